@@ -15,6 +15,8 @@ library reports for what it dispatched, `traffic` = PMC bytes per launch of exac
 this box's host cores on a bounded sample of the same workload (two builds: the exact one and numba's fastmath flag set),
 `extra.slab_share_to_self` = the N-GPU slab step of this grid measured on this one GPU with the halo exchange sent to self.
 The N > 1 line carries `rccl`: what RCCL reports about its communicator (ranks, devices, PCI bus ids).
+`--dump-outputs DIR` writes the state the last timed step left (N > 1: gathered on rank 0) to DIR/state.npy; the field is seeded, so two
+builds run with the same arguments can be compared value for value.
 """
 
 from __future__ import annotations
@@ -36,6 +38,8 @@ for _p in (ROOT, ROOT / "py-pde_amd"):
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md); measured copy ceiling ~6290 GB/s
 BYTES_PER_CELL_STEP = 16  # fp64: 1 read + 1 write per cell
+DUMP_MAX_VALUES = 1 << 22  # --dump-outputs: an array with more values is written as a seeded sample of this many (fp64: 32 MiB per dump)
+DUMP_SEED = 20240229
 
 
 def parse_args():
@@ -59,6 +63,9 @@ def parse_args():
     ap.add_argument("--repeats", type=int, default=9,
                     help="the timed region (EXACTLY --steps steps between two synchronisations) is run this many times; value / ms_per_step "
                          "are the MEDIAN, the line carries every repetition and the minimum (SURVEY.md 8d: min / median of >= 5)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the timed path computed in its last step - the state a caller of the Euler loop receives - "
+                         "as DIR/state.npy (float64; above DUMP_MAX_VALUES values a fixed seeded sample), so that two builds can be compared output for output")
     return ap.parse_args()
 
 
@@ -67,6 +74,25 @@ def _stats(samples_ms: list[float]) -> dict:
     s = sorted(samples_ms)
     med = s[len(s) // 2] if len(s) % 2 else 0.5 * (s[len(s) // 2 - 1] + s[len(s) // 2])
     return {"n": len(s), "min": round(s[0], 5), "median": round(med, 5), "max": round(s[-1], 5), "samples": [round(v, 5) for v in samples_ms]}
+
+
+def dump_outputs(directory: str, arrays: dict, max_values: int = DUMP_MAX_VALUES) -> dict:
+    """`--dump-outputs DIR`: every array as DIR/<name>.npy in float64.  An array of more than `max_values` values is written as its values at
+    `max_values` flat (C order) indices drawn once from `default_rng(DUMP_SEED)` - the same indices in every run and every build, for they
+    depend on the array's size alone.  Returns what the JSON line says about the files."""
+    out_dir = Path(directory)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    written = {}
+    for name, arr in arrays.items():
+        arr = np.ascontiguousarray(arr, dtype=np.float64)
+        entry = {"file": f"{name}.npy", "dtype": "float64", "of_shape": list(arr.shape), "sampled": arr.size > max_values}
+        if entry["sampled"]:
+            entry["sample"] = f"values at np.sort(default_rng({DUMP_SEED}).integers(0, {arr.size}, size={max_values})) of the flattened array"
+            arr = arr.reshape(-1)[np.sort(np.random.default_rng(DUMP_SEED).integers(0, arr.size, size=max_values))]
+        entry["shape"] = list(arr.shape)
+        np.save(out_dir / f"{name}.npy", arr)
+        written[name] = entry
+    return written
 
 
 def cpu_baseline(n: int, seconds: float) -> dict:
@@ -195,6 +221,8 @@ def bench_single(args) -> dict:
             cur, nxt = nxt, cur
     wall_stats = _stats([w / args.steps * 1e3 for w in walls])
     wall = wall_stats["median"] * 1e-3 * args.steps
+    # the state the last timed step left (after the clocks stopped; the measurements below read it, none writes its valid cells)
+    outputs = dump_outputs(args.dump_outputs, {"state": (a if cur == a.ptr else b).get_valid(stream=stream)}) if args.dump_outputs else None
     kernel_stats = _stats(kernel_ms)
     t_kernel = kernel_stats["median"] * 1e-3
     # device-copy ceiling of THIS GPU on the same bytes: hipMemcpyDtoD of the state = 1 read + 1 write per cell
@@ -252,6 +280,8 @@ def bench_single(args) -> dict:
         },
         "device": backend.device_name,
     }
+    if outputs is not None:
+        out["outputs"] = outputs
     t_gpu = time.perf_counter()
     out["phase_seconds_main"] = round(t_gpu - t_start, 2)
     if not args.no_extra:
@@ -678,6 +708,13 @@ def bench_distributed(args) -> dict:
         if out is not cur:
             cur, nxt = nxt, cur
     ok = all(control.allgather(bool(np.isfinite(stepper.gather_local(cur)).all())))
+    outputs = None
+    if args.dump_outputs:
+        # the gathered state the last timed step left, written by rank 0 (every rank takes part in the gather)
+        final = gather_to_rank0(cur)
+        if rank == 0:
+            outputs = dump_outputs(args.dump_outputs, {"state": final})
+        del final
     if blocks:
         info = {"decomposition": [int(d) for d in stepper.dims], "two_steps_per_sweep": bool(stepper.block2), "fast_block_loop": bool(stepper.block2),
                 "cells_per_rank": [int(v) for v in stepper.mesh.local_shape]}
@@ -728,7 +765,7 @@ def bench_distributed(args) -> dict:
                 "note": "per GPU, rank 0; wall-clock of K steps of the serial two-step loop on a grid of the slab's shape (no HIP events: the "
                         "loop runs on the library's own streams); the exchange and its choreography are what `per_rank` shows on top"}
     return {"wall": wall_stats["median"] * 1e-3 * args.steps, "wall_stats": wall_stats, "rank": rank, "finite": ok, "info": info, "parity": parity,
-            "state_sha256": digest, "per_rank": per_rank, "roofline": roofline, "rccl": rccl}
+            "state_sha256": digest, "per_rank": per_rank, "roofline": roofline, "rccl": rccl, "outputs": outputs}
 
 
 def _free_port() -> int:
@@ -793,6 +830,8 @@ def main():
         wall = r["wall"]
         line = {"roofline": r["roofline"], "cpu_baseline": None, "slab": r["info"], "finite": r["finite"], "parity": r["parity"],
                 "state_sha256_after_6_steps": r["state_sha256"], "per_rank": r["per_rank"], "rccl": r["rccl"]}
+        if r["outputs"] is not None:
+            line["outputs"] = r["outputs"]
         if "decomposition" in r["info"]:
             parallelism = (f"blocks{'x'.join(str(d) for d in r['info']['decomposition'])} (boxes with two-layer halos incl. edges, one RCCL message per "
                            "neighbouring rank, rim kernel + interior sweep)")
@@ -803,7 +842,7 @@ def main():
         ngpu = 1
         wall = r["wall"]
         line = {"roofline": r["roofline"]}
-        for key in ("roofline_operator", "roofline_operators", "parity", "extra", "extra_error"):
+        for key in ("roofline_operator", "roofline_operators", "parity", "extra", "extra_error", "outputs"):
             if key in r:
                 line[key] = r[key]
         if isinstance(line.get("parity"), dict):

@@ -18,8 +18,22 @@ REF = Path(os.environ.get("PDEHIP_REFERENCE") or "/root/reference")
 REAL = os.environ.get("PDEHIP_DROPIN_REAL", "") == "1"
 
 
-def available() -> bool:
-    return (REF / "pde").exists()
+def available(part: str = "pde") -> bool:
+    """True where this part of the reference (its package, its ``tests``) can be read; a directory this user may not enter counts as absent."""
+    try:
+        return (REF / part).is_dir()
+    except OSError:
+        return False
+
+
+def import_reference():
+    """The reference package ``pde``, or None where it is absent (the caller skips the tests that drive it)."""
+    if not available():
+        return None
+    add_to_path()
+    import pde
+
+    return pde
 
 
 def add_to_path() -> None:

@@ -15,14 +15,13 @@ tests/test_hip_adaptive_euler.py.
 from __future__ import annotations
 
 import json
-import sys
 from pathlib import Path
 
 import numpy as np
 import pytest
 
 from adaptive_euler_cases import solve  # noqa: E402
-from refpath import REF  # noqa: E402
+from refpath import import_reference  # noqa: E402
 
 GOLD = np.load(Path(__file__).parent / "golden" / "adaptive_euler.npz")
 CASES = {c["id"]: c for c in json.loads(str(GOLD["cases"]))}
@@ -64,22 +63,23 @@ def test_oracle_combine_against_numpy(dtype):
     assert np.isnan(err)          # np.abs(...).max() propagates NaN: the controller then shrinks the step (solvers/base.py:577-580)
 
 
-if not (REF / "pde").exists():
-    pytest.skip("py-pde (reference) not available", allow_module_level=True)
-if str(REF) not in sys.path:
-    sys.path.append(str(REF))
+# the tests above need the oracle only; the ones below drive the reference package and are skipped where it is absent
+pde = import_reference()
+needs_reference = pytest.mark.skipif(pde is None, reason="py-pde (reference) not available")
 
-import pde  # noqa: E402
 import shimlib  # noqa: E402
 from helpers import max_rel  # noqa: E402
 
 
 @pytest.fixture(autouse=True)
 def _scipy_operators(monkeypatch):
+    if pde is None:
+        return
     monkeypatch.setitem(pde.config, "default_backend", "scipy")     # operators of the reference's numpy path (numba is not installed)
     monkeypatch.setitem(pde.config, "backend.torch.compile", False)
 
 
+@needs_reference
 @pytest.mark.parametrize("fused", [False, True], ids=["unfused", "fused"])
 @pytest.mark.parametrize("cid", list(CASES))
 def test_goldens_through_the_real_pypde(cid, fused):
@@ -104,6 +104,7 @@ def test_goldens_through_the_real_pypde(cid, fused):
     assert info["solver"]["dt_statistics"]["mean"] == pytest.approx(float(GOLD[f"{cid}/dt_mean"]), rel=1e-9)
 
 
+@needs_reference
 @pytest.mark.parametrize("cid", ["diffusion_time_bc_2d", "cahn_hilliard_time_bc_2d", "diffusion_time_bc_interrupts"])
 def test_goldens_are_what_the_reference_computes_now(cid):
     res, info = solve(CASES[cid], pde, GOLD[f"{cid}/input"], "numpy")
@@ -117,6 +118,7 @@ def _judge_probe(eq, backend, grid, t_range=1.03, dt=0.01):
     return np.array(res.data), info["solver"]["steps"]
 
 
+@needs_reference
 @pytest.mark.parametrize("fused", [False, True], ids=["unfused", "fused"])
 def test_the_three_probes_of_the_round3_review(fused):
     """16 x 12 grid, t_range 1.03, dt 0.01: 90 steps with `sin(t)+y*0.1` on a face (was 62), 164 with `sin(3*t)` in the
@@ -150,6 +152,7 @@ def test_the_three_probes_of_the_round3_review(fused):
     assert n == nref and max_rel(got, ref) < 1e-10
 
 
+@needs_reference
 @pytest.mark.parametrize("seed", [0, 1, 2, 3, 4, 6, 7, 9, 10, 11, 12])
 def test_fuzz_with_explicit_time_dependence(seed):
     """Random class PDEs whose conditions depend on time and position, random expression PDEs with `t` in the equation, initial step
@@ -224,6 +227,7 @@ def test_fuzz_with_explicit_time_dependence(seed):
     assert np.isfinite(ref).all() and max_rel(got, ref) < 1e-9, (type(eq).__name__, shape, periodic, kw)
 
 
+@needs_reference
 def test_python_driven_loop_equals_the_c_loop(monkeypatch):
     """PDEHIP_ADAPTIVE_LOOP=0 / PDEHIP_EXPR_LOOP=0 drive the same attempts from Python (the path hooks and Python-function conditions
     take): bit-identical states and equal counts."""

@@ -9,12 +9,11 @@ written with its field operators: ``pde.PDE`` needs numba there) and its torch b
 
 from __future__ import annotations
 
-import sys
 from pathlib import Path
 
 import numpy as np
 import pytest
-from refpath import REF  # noqa: E402
+from refpath import import_reference  # noqa: E402
 
 
 def test_symbolic_split_against_complex_arithmetic():
@@ -71,18 +70,18 @@ def test_oracle_modulus_norm(dtype):
     assert np.isnan(O.max_abs_pairs(oracle_grid(grid, dtype), 2, to_full(grid, planar)))
 
 
-if not (REF / "pde").exists():
-    pytest.skip("py-pde (reference) not available", allow_module_level=True)
-if str(REF) not in sys.path:
-    sys.path.append(str(REF))
+# the tests above need the oracle only; the ones below drive the reference package and are skipped where it is absent
+pde = import_reference()
+needs_reference = pytest.mark.skipif(pde is None, reason="py-pde (reference) not available")
 
-import pde  # noqa: E402
 import shimlib  # noqa: E402
 from helpers import max_rel  # noqa: E402
 
 
 @pytest.fixture(autouse=True)
 def _scipy_operators(monkeypatch):
+    if pde is None:
+        return
     monkeypatch.setitem(pde.config, "default_backend", "scipy")
     monkeypatch.setitem(pde.config, "backend.torch.compile", False)
 
@@ -98,7 +97,7 @@ def hip(request):
 _BC = {"x": {"value": 1 + 2j}, "y": "periodic"}
 
 
-class _Schroedinger(pde.PDEBase):
+class _Schroedinger(pde.PDEBase if pde else object):
     """`PDE({'p': 'I * laplace(p)'})` for the reference's numpy solver (pde.PDE takes its operators from numba there)."""
 
     complex_valued = True
@@ -107,6 +106,7 @@ class _Schroedinger(pde.PDEBase):
         return 1j * state.laplace(_BC)
 
 
+@needs_reference
 @pytest.mark.parametrize("solver,adaptive", [("euler", False), ("runge-kutta", False), ("runge-kutta", True), ("euler", True), ("adams-bashforth", False)])
 def test_schroedinger_against_the_reference(hip, solver, adaptive):
     """VERDICT r3 "next #5": `PDE({'u': 'I*laplace(u)'})` with a complex boundary value, Euler / RK4 / RKF45 / adaptive Euler / AB2:
@@ -125,6 +125,7 @@ def test_schroedinger_against_the_reference(hip, solver, adaptive):
         assert max_rel(got, ref.data) < 1e-10
 
 
+@needs_reference
 @pytest.mark.parametrize("solver,adaptive", [("euler", False), ("runge-kutta", True)])
 def test_nonlinear_complex_equation(hip, solver, adaptive):
     """Gross-Pitaevskii-like right-hand side with a complex coefficient, `Abs`, `conjugate` and a complex Neumann value; yardstick: the
@@ -150,6 +151,7 @@ def test_nonlinear_complex_equation(hip, solver, adaptive):
     assert max_rel(np.array(res.data), ref.data) < 1e-10
 
 
+@needs_reference
 def test_axis_derivatives_and_gradient_squared_of_complex_fields(hip):
     """`d_dx`, `d2_dy2` and `gradient_squared` of a complex field inside an expression (complex boundary values, one periodic axis) against the
     reference's numpy solver around the same right-hand side written with its field operators."""
@@ -181,6 +183,7 @@ def test_axis_derivatives_and_gradient_squared_of_complex_fields(hip):
             assert max_rel(np.array(res.data), ref.data) < 1e-10, (which, solver)
 
 
+@needs_reference
 def test_two_complex_fields_and_a_class_pde(hip):
     """A collection of two complex scalar fields (coupled), and DiffusionPDE on a complex state (linear: acts on the parts)."""
     grid = pde.UnitGrid([9, 7], periodic=[True, False])
@@ -198,6 +201,7 @@ def test_two_complex_fields_and_a_class_pde(hip):
         assert max_rel(np.array(res.data), ref.data) < 1e-10
 
 
+@needs_reference
 def test_operators_on_complex_fields(hip):
     """`field.laplace(bc, backend="hip")`, `gradient`, `grid.make_operator(...)` on complex data: the parts through the real kernels."""
     grid = pde.CartesianGrid([[0, 4], [0, 4.5]], [8, 9], periodic=[False, True])   # (dx = 0.5: the scipy yardstick wants one spacing)
@@ -212,6 +216,7 @@ def test_operators_on_complex_fields(hip):
         grid.make_operator("gradient_squared", bc=bc, backend="hip", dtype=complex)
 
 
+@needs_reference
 def test_expression_conditions_on_complex_fields(hip):
     """Round 5 (VERDICT r4 "missing #4"): conditions given as expressions / Python functions of time and position with COMPLEX values on a
     complex field - operators and all four steppers against the reference (its scipy operators; right-hand side restated with its field
@@ -256,6 +261,7 @@ def test_expression_conditions_on_complex_fields(hip):
             grid.make_operator("laplace", bc={"x-": coupled, "x+": {"value": 0}, "y": "periodic"}, backend="hip", dtype=complex)(field.data, args={"t": 0.0})
 
 
+@needs_reference
 def test_vector_operators_of_complex_arguments(hip):
     """Round 5 (VERDICT r4 "missing #4"): `gradient` / `divergence` / `vector_laplace` / `dot` of complex arguments inside an expression
     against the reference's torch backend (Euler; it has no Runge-Kutta) and, for the adaptive schemes, against its numpy solver around the
@@ -289,6 +295,7 @@ def test_vector_operators_of_complex_arguments(hip):
         assert max_rel(np.array(res.data), ref.data) < 1e-10, (solver, adaptive)
 
 
+@needs_reference
 def test_adaptive_loops_of_complex_states_run_in_c(hip, monkeypatch):
     """Round 5 (VERDICT r4 "missing #4"): RKF45 and the adaptive Euler loop of a complex state inside ONE C call (`pdehip_jit_rk_run` /
     `pdehip_jit_euler_adaptive_run`, stage_fuse bit 1: modulus norm from an explicit error field) - the same bits and the same
@@ -326,6 +333,7 @@ def test_adaptive_loops_of_complex_states_run_in_c(hip, monkeypatch):
 _ROBIN = {"x-": {"type": "mixed", "value": 0.5 + 1.5j, "const": 0.2 - 0.3j}, "x+": {"value": 1 + 2j}, "y": "periodic"}
 
 
+@needs_reference
 @pytest.mark.parametrize("solver,adaptive", [("euler", False), ("runge-kutta", False), ("runge-kutta", True), ("euler", True)])
 @pytest.mark.parametrize("cid", ["schroedinger_robin_2d", "schroedinger_robin_3d", "expression_complex_slope_2d"])
 def test_mixed_conditions_with_complex_coefficients(hip, cid, solver, adaptive):
@@ -351,6 +359,7 @@ def test_mixed_conditions_with_complex_coefficients(hip, cid, solver, adaptive):
     assert max_rel(np.array(res.data), gold[f"{key}/final"]) < 1e-10
 
 
+@needs_reference
 def test_operators_with_complex_factor_conditions(hip):
     """`field.laplace`, `gradient`, `make_operator` on complex data with a complex Robin coefficient: the coupling terms on the host-array path."""
     grid = pde.CartesianGrid([[0, 4], [0, 4.5]], [8, 9], periodic=[False, True])
@@ -373,6 +382,7 @@ def test_operators_with_complex_factor_conditions(hip):
     assert max_rel(np.array(res.data), ref.data) < 1e-10
 
 
+@needs_reference
 def test_what_is_refused(hip):
     grid = pde.UnitGrid([6, 6])
     field = pde.ScalarField(grid, 1.0 + 1j)

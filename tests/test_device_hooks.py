@@ -4,11 +4,9 @@ with traced hooks against the reference's numpy backend; hooks that cannot be tr
 
 from __future__ import annotations
 
-import sys
-
 import numpy as np
 import pytest
-from refpath import REF  # noqa: E402
+from refpath import import_reference  # noqa: E402
 
 from pde_hip.hooks import trace_hook
 
@@ -87,16 +85,15 @@ def test_tracer_refuses_what_is_not_pointwise():
         assert trace_hook(hook, 0.0, (4, 4), np.float64) is None
 
 
-if not (REF / "pde").exists():
-    pytest.skip("py-pde (reference) not available", allow_module_level=True)
-if str(REF) not in sys.path:
-    sys.path.append(str(REF))
+# the tests above need the oracle only; the ones below drive the reference package and are skipped where it is absent
+pde = import_reference()
+needs_reference = pytest.mark.skipif(pde is None, reason="py-pde (reference) not available")
 
-import pde  # noqa: E402
 import shimlib  # noqa: E402
 from helpers import max_rel  # noqa: E402
 
 
+@needs_reference
 @pytest.mark.parametrize("solver,adaptive", [("euler", False), ("runge-kutta", False), ("runge-kutta", True), ("euler", True)])
 def test_traced_hook_runs_on_the_device(monkeypatch, solver, adaptive):
     """`pde.PDE(..., post_step_hook=...)` with a clipping hook that also depends on time: no download / upload per step (counted), equal
@@ -144,6 +141,7 @@ def test_traced_hook_runs_on_the_device(monkeypatch, solver, adaptive):
     assert counts["down"] <= 2, counts      # the final read(s) only - with the host path: one per step
 
 
+@needs_reference
 @pytest.mark.parametrize("solver,adaptive", [("euler", False), ("runge-kutta", False), ("runge-kutta", True), ("euler", True)])
 @pytest.mark.parametrize("interval", [0.02, 0.05])
 def test_traced_hook_with_a_tracker_that_splits_the_run(monkeypatch, solver, adaptive, interval):
@@ -201,6 +199,7 @@ def test_traced_hook_with_a_tracker_that_splits_the_run(monkeypatch, solver, ada
     assert max_rel(got, ref.data) < 1e-10 and got.max() <= 0.8
 
 
+@needs_reference
 def test_untraceable_hook_keeps_the_host_path(monkeypatch):
     monkeypatch.setitem(pde.config, "default_backend", "scipy")
     calls = []

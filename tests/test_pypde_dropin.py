@@ -18,8 +18,8 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-from refpath import REAL, REF  # noqa: E402
-if not (REF / "pde").exists():
+from refpath import REAL, REF, available  # noqa: E402
+if not available():
     pytest.skip("py-pde (reference) not available", allow_module_level=True)
 if str(REF) not in sys.path:
     sys.path.append(str(REF))

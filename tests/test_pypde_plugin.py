@@ -17,8 +17,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from refpath import REF  # noqa: E402
-if not (REF / "pde").exists():
+from refpath import REF, available  # noqa: E402
+if not available():
     pytest.skip("py-pde (reference) not available", allow_module_level=True)
 if str(REF) not in sys.path:
     sys.path.append(str(REF))

@@ -20,10 +20,10 @@ import pytest
 
 HERE = Path(__file__).resolve().parent
 sys.path.insert(0, str(HERE))
-from refpath import REAL, REF  # noqa: E402
+from refpath import REAL, REF, available  # noqa: E402
 
 REF_TESTS = REF / "tests"
-if not REF_TESTS.exists():
+if not available("tests"):
     pytest.skip("py-pde (reference) not available", allow_module_level=True)
 
 # file -> ids (substring of the node id) that are expected to FAIL today, with the reason
