@@ -41,7 +41,7 @@ extern "C" {
 #endif
 
 #define PDEHIP_MAX_DIM 3
-#define PDEHIP_ABI_VERSION 7
+#define PDEHIP_ABI_VERSION 8
 
 enum { PDEHIP_F64 = 0, PDEHIP_F32 = 1 };
 /* derivative flavour, pde/backends/numba/operators/cartesian.py:386-587 `method` */
@@ -657,6 +657,50 @@ int pdehip_jit_rk_run(const pdehip_grid_t *g, const pdehip_jit_pass_t *passes, i
 int pdehip_jit_euler_adaptive_run(const pdehip_grid_t *g, const pdehip_jit_pass_t *passes, int npasses, void *const *fixed, int nfixed,
                                   int ncomp, void *y, void *ynew, void *const *work3_host, double *err_dev, pdehip_adaptive_t *ctl,
                                   int stage_fuse, void *bc_program, void **result, void *stream);
+
+/* ---- implicit Euler and Crank-Nicolson (ABI version 8) -------------------------------------------------------------------
+ * The reference's fixed-point solvers: pde/solvers/implicit.py:74-110 (`state = state_t + dt * rhs(state, t + dt)`, first estimate
+ * with rhs(state_t, t)) and pde/solvers/crank_nicolson.py:80-113 (`state_cn = state_t + dt / 2 * (rhs(state, t + dt) + rate_t)`,
+ * `state = alpha * state + (1 - alpha) * state_cn`), both iterated until `sum |state - prev|^2 / state.size < maxerror^2` or `maxiter`
+ * iterations have passed (then the reference raises ConvergenceError).  One call advances `nsteps` steps of size dt.
+ *
+ * An iteration is ONE sweep where the stage kernels carry it (diffusion: lap_march_kernel with the fixed-point epilogue - right-hand
+ * side, update and the sweep's share of the norm, fp64 partial sums, one per wave in a fixed slot, no atomics), else the slope
+ * sweep and one pointwise kernel for update and norm (Cahn-Hilliard, 1-D, systems).  A one-workgroup kernel sums the partials in a
+ * fixed order and does the stop test on the device; the host enqueues batches of iterations, whose launches return at entry once
+ * the step is over, and reads the 64-byte control block through pinned memory once per batch (`batch` = 0: the iterations of the
+ * step before plus one, 2 at the start).  Results do not depend on the batch size.
+ *
+ * work4 = two arrays of the state's size (iterates; the state array itself is the third buffer of the rotation), the array of
+ * rate_t (Crank-Nicolson, else NULL), a scratch array for the slope (may be NULL: status 2 and nothing advanced when the right-hand
+ * side needs it).  ctl_dev: device memory of pdehip_fixedpoint_ctl_bytes bytes.  *result names the array that holds the state
+ * afterwards (the state array or one of the two iterates).  Time-dependent faces (bc_program): the first estimate of implicit Euler
+ * and rate_t see them at t, everything else at t + dt; rhs->t is the time of the first step. */
+typedef struct pdehip_fixedpoint {
+    int32_t scheme;              /* 0: implicit Euler, 1: Crank-Nicolson */
+    int32_t maxiter;             /* >= 1 */
+    double explicit_fraction;    /* Crank-Nicolson: alpha */
+    double maxerror2;            /* maxerror ** 2 */
+    int32_t batch;               /* iterations enqueued between two reads of the control block; 0: adaptive */
+    int32_t last_iterations;     /* in / out: iterations of the step before (0: none yet) */
+    int64_t steps_done;          /* out (+=): completed steps */
+    int64_t evaluations;         /* out (+=): right-hand-side evaluations, n + 2 (implicit) / n + 3 (Crank-Nicolson) per step of n iterations */
+    int32_t status;              /* out: 0 done, 1 a step did not converge within maxiter (later steps not started; state unspecified), 2 scratch needed */
+    int32_t fused;               /* out: 1 = the iterations ran as one sweep each */
+    double err;                  /* out: the norm of the last iteration */
+    int32_t *iterations;         /* NULL or host array of nsteps entries: iterations of every step */
+} pdehip_fixedpoint_t;
+int pdehip_fixedpoint_ctl_bytes(const pdehip_grid_t *g, int ncomp, size_t *bytes);
+int pdehip_fixedpoint_run(const pdehip_grid_t *g, const pdehip_rhs_t *rhs, pdehip_fixedpoint_t *fp, double dt, int64_t nsteps, void *state_full,
+                          void *const *work4_host, void *ctl_dev, size_t ctl_bytes, void **result, void *stream);
+/* The same loops around the passes of an expression PDE (passes as in pdehip_jit_rk_run: -1 - k as `src` / `extras` is component k of the
+ * iterate, as `out` component k of the rate; the passes that write a rate compute `p[0] * F` and get p[0] = 1, p[1] = the time).  A
+ * single-component expression whose last pass runs on the vectorised kernel takes the fixed-point epilogue in that pass (stage_fuse bit 0);
+ * systems and complex states (planar (re, im) pairs; stage_fuse bit 1: `state.size` counts a pair once) use the pointwise kernel on all
+ * components at once.  Arrays of work4 hold ncomp components each. */
+int pdehip_jit_fixedpoint_run(const pdehip_grid_t *g, const pdehip_jit_pass_t *passes, int npasses, void *const *fixed, int nfixed, int ncomp,
+                              pdehip_fixedpoint_t *fp, double dt, double t0, int64_t nsteps, void *state_full, void *const *work4_host,
+                              void *ctl_dev, size_t ctl_bytes, int stage_fuse, void *bc_program, void **result, void *stream);
 
 #ifdef __cplusplus
 }

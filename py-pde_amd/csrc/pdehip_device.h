@@ -82,6 +82,46 @@ __device__ __forceinline__ long xcd_swizzle(long bid, long nblocks)
     return (bid % 8) * per + bid / 8;
 }
 
+// ---- fixed-point solvers (implicit Euler, Crank-Nicolson): control block and the deterministic convergence norm ----------
+// One device allocation: this block, then (at kFixedPointSlots doubles from its start) one partial sum per wave of the sweep that
+// ran last.  The stage sweeps get its address as LapArgs::st_err (st_kind 5).  Kernels only READ `stop`, at entry; the final sum
+// (fixedpoint_finish_kernel) is the only writer after the start of a step.  Nothing on the device waits for it.
+struct FixedPointCtl {
+    double err;          // mean |new - prev|^2 of the iteration that ran last
+    long long evals;     // right-hand-side evaluations counted on the device (one per iteration)
+    int iters;           // iterations done in this step
+    int converged;       // the stop test err < maxerr2 held
+    int failed;          // maxiter iterations without convergence
+    int stop;            // converged | failed: every later launch of the step returns at once
+    int nslots;          // partial sums the last sweep wrote (waves of its launch)
+    int maxiter;
+    double maxerr2;
+    double size;         // values the mean is taken over (complex pairs count once)
+    int capacity;        // slots behind the block
+    int reserved;
+};
+constexpr int kFixedPointSlots = 8;   // doubles in front of the partial sums (sizeof(FixedPointCtl) <= 64)
+static_assert(sizeof(FixedPointCtl) <= kFixedPointSlots * sizeof(double), "the control block overlaps its partial sums");
+
+// entry of a fixed-point sweep: one uniform scalar load
+__device__ __forceinline__ bool fixedpoint_stopped(const double *ctl) { return ((const FixedPointCtl *)ctl)->stop != 0; }
+// ... and, when the sweep runs, the number of partial sums it will leave (waves of the launch; written by its first thread)
+__device__ __forceinline__ void fixedpoint_announce(double *ctl, long nslots)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0) ((FixedPointCtl *)ctl)->nslots = (int)nslots;
+}
+// end of a fixed-point sweep: butterfly sum over the wave (both partners add the same two numbers: every lane ends with the same
+// bits, in an order fixed by the lane numbers), one store per wave to its slot.  No atomics.
+// `slot`: the wave's number in the launch - fixed by the launch geometry alone.  (The stencil sweeps are short of SCALAR registers - some
+// instances sit at 100 of 102 -: they compute the slot from threadIdx at entry, which keeps it in a vector register, announce the slot count
+// there too, where `nblocks` is live anyway, and never read blockDim / gridDim, which would cost the pointer to the dispatch packet.)
+__device__ __forceinline__ void fixedpoint_wave_partial(double *ctl, double esum, int slot)
+{
+#pragma unroll
+    for (int ofs = 32; ofs >= 1; ofs >>= 1) esum = esum + __shfl_xor(esum, ofs, 64);
+    if ((threadIdx.x & 63) == 0 && slot < ((const FixedPointCtl *)ctl)->capacity) ctl[kFixedPointSlots + slot] = esum;   // (the buffer holds any launch: pdehip_fixedpoint_ctl_bytes)
+}
+
 template <int MODE>
 __device__ __forceinline__ double epilogue(double lap, double c, double yv, double s1, double s2, double gamma)
 {
@@ -126,6 +166,12 @@ struct LapArgs {
     //   st_kind 2: st_out = y + c1*k1 + c3*k3 + c4*k4 + c5*k5 and *st_err = max |error estimate| with k6 = k; st_k = {k1, k3, k4, k5},
     //              `out` is not written                                          (end of an RKF45 attempt, runge_kutta.py:147-150)
     //   st_kind 3: out = k (the rate, s2 = 1), st_out = y + st_c[5] * (1.5*k - 0.5*st_k[0])   (Adams-Bashforth step, adams_bashforth.py:44)
+    //   st_kind 5: one fixed-point iteration (pde/solvers/implicit.py:88-104, crank_nicolson.py:92-108), k = rhs(in) with s2 = 1, `out` is not
+    //              written.  st_k[1] = prev, the previous iterate (the input of the sweep, or of the first pass of a multi-pass expression).
+    //              st_k[0] == NULL: st_out = y + st_c[5] * k (implicit Euler, st_c[5] = dt);  else st_out = st_c[0] * prev +
+    //              st_c[1] * (y + st_c[5] * (k + st_k[0]))  (Crank-Nicolson: st_k[0] = rate_t, st_c[5] = dt/2, st_c[0] = alpha, st_c[1] = 1 - alpha).
+    //              st_err = the FixedPointCtl block: the sweep returns at once when its `stop` is set, else every wave leaves its sum of
+    //              (st_out - prev)^2 in its slot behind the block.
     int st_kind;
     double *st_err;
     const void *st_y;

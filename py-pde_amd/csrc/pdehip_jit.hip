@@ -17,6 +17,7 @@
 
 #include "pdehip_common.h"
 #include "pdehip_rk_loops.h"
+#include "pdehip_fixedpoint.h"
 #include "pdehip_sources.h"   // generated: kDeviceH, kMarchInc (raw string literals)
 
 using namespace pdehip;
@@ -298,7 +299,7 @@ int jit_apply_impl(void *handle, const pdehip_grid_t *g, void *in_full, const vo
                    const StageFuse *stage, int *done)
 {
     if (done) *done = 0;
-    if (!handle || !in_full || (!out_full && !(stage && (stage->kind == 1 || stage->kind == 2 || stage->kind == 4)))) PDEHIP_FAIL(E_VALUE, "jit_apply: NULL pointer");
+    if (!handle || !in_full || (!out_full && !(stage && (stage->kind == 1 || stage->kind == 2 || stage->kind == 4 || stage->kind == 5)))) PDEHIP_FAIL(E_VALUE, "jit_apply: NULL pointer");
     if (nparams < 0 || nparams > 12) PDEHIP_FAIL(E_VALUE, "jit_apply: at most 12 scalar parameters");
     Jit *j = static_cast<Jit *>(handle);
     NGrid n;
@@ -327,8 +328,10 @@ int jit_apply_impl(void *handle, const pdehip_grid_t *g, void *in_full, const vo
         int nk = 0;
         for (int m = 0; m < 5 && stage->k[m]; m++, nk++) { a.st_k[m] = stage->k[m]; a.st_c[m] = stage->c[m]; }
         if ((stage->kind == 1 && nk != 3) || (stage->kind == 2 && (nk != 4 || !stage->err)) || (stage->kind == 4 && (nk != 2 || !stage->err)) || stage->kind < 0 ||
-            stage->kind == 3 || stage->kind > 4)
+            stage->kind == 3 || stage->kind > 5 || (stage->kind == 5 && (!stage->err || !stage->k[1])))
             PDEHIP_FAIL(E_VALUE, "jit_apply_stage: malformed stage (kind %d with %d earlier slopes)", stage->kind, nk);
+        if (stage->kind == 5)   // fixed-point iteration (internal: pdehip_jit_fixedpoint_run): k[0] = rate_t or NULL, k[1] = the previous iterate, c[0..1] = its weights
+            for (int m = 0; m < 2; m++) { a.st_k[m] = stage->k[m]; a.st_c[m] = stage->c[m]; }
         a.st_c[5] = stage->c_new;
         uintptr_t bits = (uintptr_t)a.st_y | (uintptr_t)a.st_out;
         for (int m = 0; m < 5; m++) bits |= (uintptr_t)a.st_k[m];
@@ -1058,6 +1061,7 @@ struct JitEval {
     // k_out = dt * F(in; t) and - where the last pass carries it - the combination `sf` in the same sweep (*fused)
     int slope(void *in, void *k_out, double dt, double t, const StageFuse *sf, bool *fused, void *st)
     {
+        if (sf && sf->kind == 5) return fixedpoint_slope(in, k_out, t, sf, fused, st);
         *fused = false;
         const double params[2] = {dt, t};
         PDEHIP_TRY(refresh(t, in, st));
@@ -1080,6 +1084,35 @@ struct JitEval {
         stage_fuse = -1;   // only the generic kernel covers this grid: plain pass + pointwise combination from now on
         pdehip_jit_pass_t again = last;
         again.exchange = nullptr;   // (its operand has just been exchanged)
+        return run_passes(g, &again, 1, fixed, (char *)in, (char *)k_out, comp_bytes, params, st);
+    }
+    const char *sweep_name() const { return "pde_kernel (run-time build of lap_march_body, LAP_CUSTOM with the stage epilogue)"; }
+    // One fixed-point iteration (StageFuse kind 5, pdehip_fixedpoint.h): every pass but the last as usual, the last one with the update and
+    // the convergence norm in its sweep where it runs on the vectorised kernel; else (systems, 1-D, generic kernel) the slope into
+    // `k_out` and the caller's pointwise kernel.  sf->k[1] is the iterate the passes start from.
+    int fixedpoint_slope(void *in, void *k_out, double t, const StageFuse *sf, bool *fused, void *st)
+    {
+        *fused = false;
+        const double params[2] = {1.0, t};
+        PDEHIP_TRY(refresh(t, in, st));
+        const pdehip_jit_pass_t &last = passes[npasses - 1];
+        const bool try_stage = stage_fuse > 0 && ncomp == 1 && last.out == -1;
+        if (!try_stage && !k_out) { set_error("jit_fixedpoint_run: this right-hand side needs the scratch array for its slope"); return FP_NEED_SCRATCH; }
+        PDEHIP_TRY(run_passes(g, passes, npasses, fixed, (char *)in, (char *)k_out, comp_bytes, params, st, try_stage ? 1 : 0));
+        if (!try_stage) return 0;
+        auto arr = [&](int32_t idx) -> void * {
+            if (idx == PDEHIP_JIT_NONE) return nullptr;
+            return idx >= 0 ? fixed[idx] : (void *)((char *)in + (size_t)(-1 - idx) * comp_bytes);
+        };
+        const void *ex[3] = {arr(last.extras[0]), arr(last.extras[1]), arr(last.extras[2])};
+        int done = 0;
+        PDEHIP_TRY(exchange_operand(g, last, arr(last.src), st));
+        PDEHIP_TRY(jit_apply_impl(last.handle, g, arr(last.src), ex, nullptr, params, 2, last.faces, st, sf, &done));
+        if (done) { *fused = true; return 0; }
+        stage_fuse = -1;   // only the generic kernel covers this grid: plain pass + pointwise update from now on
+        if (!k_out) { set_error("jit_fixedpoint_run: this grid needs the scratch array for the slope"); return FP_NEED_SCRATCH; }
+        pdehip_jit_pass_t again = last;
+        again.exchange = nullptr;
         return run_passes(g, &again, 1, fixed, (char *)in, (char *)k_out, comp_bytes, params, st);
     }
     int lincomb(void *out, const void *y, int n, const double *c, const void *const *k, void *st) { return pdehip_lincomb(g, ncomp, out, y, n, c, k, st); }
@@ -1171,6 +1204,31 @@ int pdehip_jit_euler_adaptive_run(const pdehip_grid_t *g, const pdehip_jit_pass_
     if (!ctl) PDEHIP_FAIL(E_VALUE, "jit_euler_adaptive_run: NULL pointer");
     return jit_loop_run("jit_euler_adaptive_run", 1, g, passes, npasses, fixed, nfixed, ncomp, y, ynew, work3_host, err_dev, 0.0, 0.0, 0, ctl,
                         stage_fuse, bc_program, result, stream);
+}
+
+int pdehip_jit_fixedpoint_run(const pdehip_grid_t *g, const pdehip_jit_pass_t *passes, int npasses, void *const *fixed, int nfixed, int ncomp,
+                              pdehip_fixedpoint_t *fp, double dt, double t0, int64_t nsteps, void *state_full, void *const *work4_host,
+                              void *ctl_dev, size_t ctl_bytes, int stage_fuse, void *bc_program, void **result, void *stream)
+{
+    if (!g || !passes || (nfixed > 0 && !fixed)) PDEHIP_FAIL(E_VALUE, "jit_fixedpoint_run: NULL pointer");
+    if (npasses < 1 || ncomp < 1) PDEHIP_FAIL(E_VALUE, "jit_fixedpoint_run: bad pass / component count");
+    if ((stage_fuse & 2) && ncomp % 2) PDEHIP_FAIL(E_VALUE, "jit_fixedpoint_run: complex pairs need an even number of components");
+    NGrid n;
+    PDEHIP_TRY(norm_grid(g, &n));
+    for (int q = 0; q < npasses; q++) {
+        const pdehip_jit_pass_t &p = passes[q];
+        if (!p.handle) PDEHIP_FAIL(E_VALUE, "jit_fixedpoint_run: pass %d has no handle", q);
+        const int32_t idx[5] = {p.src, p.extras[0], p.extras[1], p.extras[2], p.out};
+        for (int m = 0; m < 5; m++) {
+            if (idx[m] == PDEHIP_JIT_NONE && m != 0 && m != 4) continue;
+            if (idx[m] == PDEHIP_JIT_NONE || idx[m] >= nfixed || idx[m] < -ncomp)
+                PDEHIP_FAIL(E_VALUE, "jit_fixedpoint_run: pass %d refers to array %d (fixed: %d, components: %d)", q, (int)idx[m], nfixed, ncomp);
+        }
+    }
+    JitEval ev{g, passes, npasses, fixed, ncomp, (size_t)n.pc * elem_size(n.dtype), (stage_fuse & 1) ? 1 : 0, bc_program};
+    // `state.size` of the reference: every stored value, a complex value once (implicit.py:99-102 sums |d|^2 = re^2 + im^2)
+    const double size = (double)n.n[0] * (double)n.n[1] * (double)n.n[2] * (double)((stage_fuse & 2) ? ncomp / 2 : ncomp);
+    return fp::run(ev, g, ncomp, size, fp, dt, t0, nsteps, state_full, work4_host, (double *)ctl_dev, ctl_bytes, result, stream);
 }
 
 }  // extern "C"

@@ -133,7 +133,7 @@ static int launch_march(const LapArgs &a0, bool y_is_in, long want_blocks, hipSt
     const bool tails = (a.n2 % VEC != 0) || (((a.n2 + 64L * VEC - 1) / (64L * VEC)) % CZ != 0);
     // streaming stores: 3-D outputs that do not fit the 256 MB Infinity Cache (a smaller field is re-read from that cache by the
     // next sweep); the whole-row tiles of aligned rows only (the hot instances)
-    const int ncomp_out = (MODE == LAP_GRAD_C || MODE == LAP_GRAD_F || MODE == LAP_GRAD_B) ? 3 : (MODE == LAP_STAGE ? 2 : 1);
+    const int ncomp_out = (MODE == LAP_GRAD_C || MODE == LAP_GRAD_F || MODE == LAP_GRAD_B) ? 3 : ((MODE == LAP_STAGE && a.st_kind != 5) ? 2 : 1);
     static const bool nt_off = getenv("PDEHIP_NO_NT") != nullptr;   // A/B aid
     const bool nt = HAS_X && !tails && !nt_off && ((double)a.n0 * a.n1 * a.n2 * sizeof(T) * ncomp_out > 192.0 * 1048576.0);
     note_kernel("lap_march_kernel<%s,%d,RY=%d,CZ=%d,WY=%d,PF=%d,mode=%d,%s,%s,%s>", sizeof(T) == 8 ? "double" : "float", VEC, RY, CZ, WY, PF, MODE, HAS_X ? "3-D" : "2-D",
@@ -391,7 +391,7 @@ int launch_laplace(const NGrid &n, const void *in, void *out, const OutStr &o, i
                    double s2, double gamma, const void *y, hipStream_t st, const InputBCs *fg, const StageFuse *stage)
 {
     if ((mode == LAP_STAGE) != (stage != nullptr)) PDEHIP_FAIL(E_RUNTIME, "internal: stage epilogue without / with a stage descriptor");
-    if (!in || (!out && !(stage && (stage->kind == 1 || stage->kind == 2 || stage->kind == 4)))) PDEHIP_FAIL(E_VALUE, "laplace: NULL array pointer");
+    if (!in || (!out && !(stage && (stage->kind == 1 || stage->kind == 2 || stage->kind == 4 || stage->kind == 5)))) PDEHIP_FAIL(E_VALUE, "laplace: NULL array pointer");
     if (mode == LAP_EULER && !y) PDEHIP_FAIL(E_VALUE, "laplace_euler: y is NULL");
     LapArgs a;
     memset(&a, 0, sizeof(a));
@@ -421,6 +421,10 @@ int launch_laplace(const NGrid &n, const void *in, void *out, const OutStr &o, i
         if (stage->kind == 2 && (nk != 4 || !stage->err)) PDEHIP_FAIL(E_RUNTIME, "internal: the RKF45 update needs four earlier slopes and the error cell");
         if (stage->kind == 3 && nk != 1) PDEHIP_FAIL(E_RUNTIME, "internal: the Adams-Bashforth update needs the previous rate");
         if (stage->kind == 4 && (nk != 2 || !stage->err || stage->k[1] != in)) PDEHIP_FAIL(E_RUNTIME, "internal: the adaptive Euler update needs the rate, the half step as the input of the sweep and the error cell");
+        if (stage->kind == 5) {   // fixed-point iteration: k[0] = rate_t or NULL, k[1] = the previous iterate = the input, c[0..1] = its weights, err = the control block
+            if (!stage->err || stage->k[1] != in) PDEHIP_FAIL(E_RUNTIME, "internal: the fixed-point update needs the previous iterate as the input of the sweep and the control block");
+            for (int m = 0; m < 2; m++) { a.st_k[m] = stage->k[m]; a.st_c[m] = stage->c[m]; }
+        }
         a.st_err = stage->err;
         a.st_c[5] = stage->c_new;
     }

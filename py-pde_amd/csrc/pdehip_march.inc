@@ -41,6 +41,12 @@ __device__ __forceinline__ void lap_march_body(const LapArgs &a)
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform -> SGPR
     const unsigned lo = (unsigned)lane * VEC;                        // the lane's only address term
 
+    // fixed-point iteration (st_kind 5) of a step that has already converged or failed: nothing to do (uniform: one scalar load)
+    if (kStage && a.st_kind == 5) {
+        if (fixedpoint_stopped(a.st_err)) return;
+        fixedpoint_announce(a.st_err, a.nblocks * WY);   // (no strip in front of a stage sweep)
+    }
+    const int fp_slot = (int)blockIdx.x * WY + (int)(threadIdx.x >> 6);   // st_kind 5: the wave's slot of the convergence norm (a vector register on purpose)
     const long bid0 = (long)blockIdx.x - a.strip_blocks;   // (a multiple of 8 workgroups in front belong to the strip of split rows)
     long bid = a.no_swizzle ? bid0 : xcd_swizzle(bid0, a.nblocks);
     const long tz = bid % a.ntz;
@@ -50,7 +56,10 @@ __device__ __forceinline__ void lap_march_body(const LapArgs &a)
 
     const long kw = tz * (CW * CZ);                 // first cell of the wave tile (valid index)
     const long j0 = ty * (WY * RY) + (long)w * RY;  // first row of the wave tile
-    if (j0 >= a.n1) return;                         // whole wave outside (no barriers are used)
+    if (j0 >= a.n1) {                               // whole wave outside (no barriers are used)
+        if (kStage && a.st_kind == 5) fixedpoint_wave_partial(a.st_err, 0.0, fp_slot);   // (its slot of the convergence norm)
+        return;
+    }
     const long i0 = xc * a.lx;
     const long i1 = (i0 + a.lx < a.n0) ? i0 + a.lx : a.n0;
 
@@ -232,6 +241,7 @@ __device__ __forceinline__ void lap_march_body(const LapArgs &a)
     }
 
     double emax = 0;   // LAP_STAGE, st_kind 2 / 4: the lane's share of the error norm
+    double esum = 0;   // st_kind 5: the lane's share of sum (new - prev)^2, cells in the order of the march
     for (long i = i0; i < i1; i++) {
         if (HAS_X) load_plane((i + PF > a.n0) ? a.n0 : i + PF, PF);   // clamped onto the upper ghost plane
 #pragma unroll
@@ -254,8 +264,8 @@ __device__ __forceinline__ void lap_march_body(const LapArgs &a)
                     for (int m = 0; m < 5; m++) {
 #pragma unroll
                         for (int q = 0; q < VEC; q++) skv[m][q] = 0;
-                        // (kind 4: when st_k[1], the half step, is the input array of this sweep its value at the cell is already in registers)
-                        if (a.st_k[m] && !(a.st_kind == 4 && m == 1 && a.st_k[1] == a.in)) skv[m] = *(const V *)((const T *)a.st_k[m] + eb + lo + c * CW);   // uniform
+                        // (kinds 4, 5: when st_k[1], the half step / the previous iterate, is the input array of this sweep its value at the cell is already in registers)
+                        if (a.st_k[m] && !((a.st_kind == 4 || a.st_kind == 5) && m == 1 && a.st_k[1] == a.in)) skv[m] = *(const V *)((const T *)a.st_k[m] + eb + lo + c * CW);   // uniform
                     }
                 }
                 V exv[3];
@@ -337,6 +347,20 @@ __device__ __forceinline__ void lap_march_body(const LapArgs &a)
                                 // pde/solvers/adams_bashforth.py:44 (ab2_combine_kernel): st_c[5] = dt, st_k[0] = the previous rate
                                 const double s = a.st_c[5] * (1.5 * kn - 0.5 * (double)skv[0][q]);
                                 stv[q] = (T)((double)syv[q] + s);
+                            } else if (a.st_kind == 5) {
+                                // fixed-point iteration, pde/solvers/implicit.py:94-97 / crank_nicolson.py:98-103 (fixedpoint_combine_kernel):
+                                // st_k[1] = the previous iterate (the input of this sweep, or of the first pass of the expression), kn = rhs(prev), syv = state_t
+                                const double pv = (a.st_k[1] == a.in) ? cen : (double)skv[1][q];
+                                double nv;
+                                if (!a.st_k[0]) {
+                                    nv = (double)syv[q] + a.st_c[5] * kn;
+                                } else {
+                                    const double cn = (double)syv[q] + a.st_c[5] * (kn + (double)skv[0][q]);
+                                    nv = a.st_c[0] * pv + a.st_c[1] * cn;
+                                }
+                                stv[q] = (T)nv;
+                                const double df = (double)stv[q] - pv;
+                                if (q < nval[c] && row_ok) esum = esum + df * df;
                             } else if (a.st_kind == 4) {
                                 // end of an adaptive Euler attempt, pde/backends/numba/_solvers.py:381-394 (euler_adaptive_combine_kernel):
                                 // the input of this sweep is the half step, kn = dt/2 * rate_midpoint, st_k[0] = the carried rate, st_c[0] = dt
@@ -416,6 +440,7 @@ __device__ __forceinline__ void lap_march_body(const LapArgs &a)
             }
             if (lane == 0 && b > *(volatile unsigned long long *)a.st_err) atomicMax((unsigned long long *)a.st_err, b);   // the cell only grows
         }
+        if (a.st_kind == 5) fixedpoint_wave_partial(a.st_err, esum, fp_slot);   // uniform
     }
 }
 

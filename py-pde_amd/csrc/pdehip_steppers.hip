@@ -6,6 +6,7 @@
 //   Cahn–Hilliard Euler    : ghosts + ch_mu (1r+1w) + ghosts + laplace_euler(mu; y=c) (2r+1w) = 5 values
 //   RK stage               : lincomb (1+j reads, 1 write) + rhs_scaled; diffusion: ONE sweep per stage (rhs_stage)
 #include "pdehip_common.h"
+#include "pdehip_fixedpoint.h"
 
 using namespace pdehip;
 
@@ -407,6 +408,39 @@ int pdehip_rkf45_attempt(const pdehip_grid_t *g, const pdehip_rhs_t *rhs, void *
     PDEHIP_TRY(rhs_scaled_at(g, rhs, tmp, w[5], dt, t0 + A45[5] * dt, stream));
     // runge_kutta.py:147-150
     return pdehip_rkf45_combine(g, 1, y, ynew, k, err_dev, stream);
+}
+
+// ---- implicit Euler / Crank-Nicolson: the fixed-point loop of pdehip_fixedpoint.h around the built-in right-hand sides ----
+namespace {
+struct FixedPointEval {
+    const pdehip_grid_t *g;
+    const pdehip_rhs_t *rhs;
+    const char *sweep_name() const { return nullptr; }   // (the stencil launchers have noted the instance)
+    // k_out = dt * rhs(in; t); with `sf` (kind 5) the iteration's update and norm in the same sweep where LAP_STAGE covers grid and
+    // faces (diffusion).  Cahn-Hilliard: the two-level sweep writes the slope, the pointwise kernel does update and norm.
+    int slope(void *in, void *k_out, double dt, double t, const StageFuse *sf, bool *fused, void *st)
+    {
+        *fused = false;
+        if (sf && rhs->kind == PDEHIP_RHS_DIFFUSION) {
+            PDEHIP_TRY(refresh_bcs(rhs, t, in, st));
+            PDEHIP_TRY(rhs_stage(g, rhs, in, nullptr, dt, *sf, st, fused));
+            if (*fused) return 0;
+        }
+        if (!k_out) { set_error("fixedpoint_run: this right-hand side needs the scratch array for its slope"); return FP_NEED_SCRATCH; }
+        return rhs_scaled_at(g, rhs, in, k_out, dt, t, st);
+    }
+};
+}  // namespace
+
+int pdehip_fixedpoint_run(const pdehip_grid_t *g, const pdehip_rhs_t *rhs, pdehip_fixedpoint_t *fp, double dt, int64_t nsteps, void *state_full,
+                          void *const *work4_host, void *ctl_dev, size_t ctl_bytes, void **result, void *stream)
+{
+    PDEHIP_TRY(check_rhs(rhs));
+    NGrid n;
+    PDEHIP_TRY(norm_grid(g, &n));
+    FixedPointEval ev{g, rhs};
+    const double size = (double)n.n[0] * (double)n.n[1] * (double)n.n[2];
+    return fp::run(ev, g, 1, size, fp, dt, rhs->t, nsteps, state_full, work4_host, (double *)ctl_dev, ctl_bytes, result, stream);
 }
 
 }  // extern "C"

@@ -21,7 +21,7 @@ from .fields import FieldCollection, ScalarField, Tensor2Field, VectorField
 from .grids import CartesianGrid, UnitGrid
 from .pdes import (PDE, AllenCahnPDE, CahnHilliardPDE, DiffusionPDE, KleinGordonPDE, KPZInterfacePDE, KuramotoSivashinskyPDE,
                    SwiftHohenbergPDE, WavePDE)
-from .solvers import Controller, EulerSolver, ExplicitSolver, RungeKuttaSolver
+from .solvers import Controller, ConvergenceError, CrankNicolsonSolver, EulerSolver, ExplicitSolver, ImplicitSolver, RungeKuttaSolver
 
 _operators.register_all(HipBackend, CartesianGrid)
 
@@ -37,11 +37,14 @@ __all__ = [
     "CahnHilliardPDE",
     "CartesianGrid",
     "Controller",
+    "ConvergenceError",
+    "CrankNicolsonSolver",
     "DiffusionPDE",
     "EulerSolver",
     "FieldCollection",
     "ExplicitSolver",
     "HipBackend",
+    "ImplicitSolver",
     "RungeKuttaSolver",
     "ScalarField",
     "Tensor2Field",

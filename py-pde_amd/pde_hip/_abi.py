@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 MAX_DIM = 3
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 F64, F32 = 0, 1
 CENTRAL, FORWARD, BACKWARD = 0, 1, 2
@@ -119,6 +119,28 @@ class Adaptive(C.Structure):
         ("stat_mean", C.c_double),
         ("stat_m2", C.c_double),
     ]
+
+
+class FixedPoint(C.Structure):
+    """``pdehip_fixedpoint_t``: parameters and results of the implicit Euler / Crank-Nicolson loops (``pdehip_fixedpoint_run``)."""
+
+    _fields_ = [
+        ("scheme", C.c_int32),
+        ("maxiter", C.c_int32),
+        ("explicit_fraction", C.c_double),
+        ("maxerror2", C.c_double),
+        ("batch", C.c_int32),
+        ("last_iterations", C.c_int32),
+        ("steps_done", C.c_int64),
+        ("evaluations", C.c_int64),
+        ("status", C.c_int32),
+        ("fused", C.c_int32),
+        ("err", C.c_double),
+        ("iterations", C.POINTER(C.c_int32)),
+    ]
+
+
+FIXEDPOINT_IMPLICIT, FIXEDPOINT_CRANK_NICOLSON = 0, 1
 
 
 def adaptive_statistics(ctl: Adaptive) -> dict:
@@ -279,6 +301,19 @@ COMM_PROTOTYPES: dict[str, list] = {
 }
 
 
+_pfp = C.POINTER(FixedPoint)
+
+# Entry points a loaded library MAY lack: name -> full argument list.  The library of the product exports all of them; the host
+# library of the CPU tests (tests/shim) predates them, is loaded through the same class and keeps working: `_Lib` binds what is
+# exported and records the rest in `_Lib.missing`; the features behind a missing entry are refused like before they existed.
+OPTIONAL_PROTOTYPES: dict[str, list] = {
+    # implicit Euler / Crank-Nicolson: the fixed-point loops with the convergence norm on the device (ABI version 8)
+    "fixedpoint_ctl_bytes": [_pg, _i, C.POINTER(C.c_size_t)],
+    "fixedpoint_run": [_pg, _pr, _pfp, _d, _i64, _vp, _pvp, _vp, C.c_size_t, _pvp, _vp],
+    "jit_fixedpoint_run": [_pg, C.POINTER(JitPass), _i, _pvp, _i, _i, _pfp, _d, _d, _i64, _vp, _pvp, _vp, C.c_size_t, _i, _vp, _pvp, _vp],
+}
+
+
 def exported_symbols() -> list[str]:
     """All symbols ``include/pdehip.h`` declares (checked by tests/test_cabi.py)."""
-    return ["pdehip_" + n for n in list(RUNTIME_PROTOTYPES) + list(COMPUTE_PROTOTYPES) + list(COMM_PROTOTYPES)]
+    return ["pdehip_" + n for n in list(RUNTIME_PROTOTYPES) + list(COMPUTE_PROTOTYPES) + list(COMM_PROTOTYPES) + list(OPTIONAL_PROTOTYPES)]

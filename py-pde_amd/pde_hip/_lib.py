@@ -89,9 +89,23 @@ class _Lib:
             fn = getattr(self._h, "pdehip_" + name)
             fn.argtypes = list(args)
             fn.restype = C.c_int
+        # entry points newer than some libraries loaded through this class (the host library of the CPU tests): bound where exported
+        self.missing: set[str] = set()
+        for name, args in _abi.OPTIONAL_PROTOTYPES.items():
+            try:
+                fn = getattr(self._h, "pdehip_" + name)
+            except AttributeError:
+                self.missing.add(name)
+                continue
+            fn.argtypes = list(args)
+            fn.restype = C.c_int
         if self._h.pdehip_abi_version() != _abi.ABI_VERSION:
             msg = "libpdehip.so ABI version mismatch - rebuild the library"
             raise ImportError(msg)
+
+    def has(self, *names: str) -> bool:
+        """Whether the loaded library exports these optional entry points (``_abi.OPTIONAL_PROTOTYPES``)."""
+        return not (set(names) & self.missing)
 
     def last_error(self) -> str:
         return self._h.pdehip_last_error().decode(errors="replace")

@@ -168,6 +168,33 @@ class AdamsBashforthSolver(SolverBase):
     name = "adams-bashforth"
 
 
+class ConvergenceError(RuntimeError):
+    """The fixed-point iteration of an implicit solver did not converge (solvers/base.py:42-43)."""
+
+
+class ImplicitSolver(SolverBase):
+    """Implicit (backward) Euler by fixed-point iteration: ``y_new = y + dt * f(y_new, t + dt)`` (solvers/implicit.py:21-110)."""
+
+    name = "implicit"
+
+    def __init__(self, pde, *, maxiter: int = 100, maxerror: float = 1e-4, backend="hip"):
+        super().__init__(pde, backend=backend)
+        self.maxiter = maxiter
+        self.maxerror = maxerror
+
+
+class CrankNicolsonSolver(SolverBase):
+    """Crank-Nicolson by fixed-point iteration: ``y_new = y + dt / 2 * (f(y_new, t + dt) + f(y, t))`` (solvers/crank_nicolson.py:21-113)."""
+
+    name = "crank-nicolson"
+
+    def __init__(self, pde, *, maxiter: int = 100, maxerror: float = 1e-4, explicit_fraction: float = 0, backend="hip"):
+        super().__init__(pde, backend=backend)
+        self.maxiter = maxiter
+        self.maxerror = maxerror
+        self.explicit_fraction = explicit_fraction
+
+
 class Controller:
     """Advance a state over ``t_range``, interrupting for trackers (solvers/controller.py:146-298).
 

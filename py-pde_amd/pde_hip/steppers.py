@@ -25,6 +25,33 @@ from .rhs import SpecRhs
 _logger = logging.getLogger("pde_hip.backend")
 
 
+def _fixedpoint_scheme(solver) -> int | None:
+    """0 / 1 for the reference's implicit Euler / Crank-Nicolson solver, recognised by the name it is registered under and its
+    parameters (not by the class name: any class may be called ``ImplicitSolver``), else None."""
+    name = getattr(solver, "name", None)
+    if not (hasattr(solver, "maxiter") and hasattr(solver, "maxerror")):
+        return None
+    if name == "implicit":
+        return _abi.FIXEDPOINT_IMPLICIT
+    if name == "crank-nicolson" and hasattr(solver, "explicit_fraction"):
+        return _abi.FIXEDPOINT_CRANK_NICOLSON
+    return None
+
+
+def _convergence_error(solver) -> type:
+    """The exception of a step that did not converge: py-pde's own for its solvers, else the mirror's."""
+    if type(solver).__module__.split(".")[0] == "pde":
+        try:
+            from pde.solvers.base import ConvergenceError
+        except ImportError:
+            pass
+        else:
+            return ConvergenceError
+    from .solvers import ConvergenceError
+
+    return ConvergenceError
+
+
 class StepperMixin:
     """The stepper-facing methods of :class:`~pde_hip.backend.HipBackendMixin`."""
 
@@ -608,6 +635,115 @@ class StepperMixin:
         post_step.expression = expr  # type: ignore[attr-defined]
         return post_step
 
+    def _make_fixedpoint_stepper(self, solver, state, scheme: int, post_step=None):
+        """Implicit Euler (``scheme`` 0, ``pde/solvers/implicit.py:74-110``) and Crank-Nicolson (1, ``pde/solvers/crank_nicolson.py:80-113``):
+        the reference's fixed-point iteration, ``pdehip_fixedpoint_run`` for the class right-hand sides and ``pdehip_jit_fixedpoint_run``
+        for expressions, systems and complex states.  Iterations, convergence norm and stop test run on the device; with
+        a post-step hook the loop is called step by step and the hook runs in between.  ``solver.info["function_evaluations"]`` counts the
+        right-hand sides really evaluated (``n + 2`` / ``n + 3`` per step of ``n`` iterations), ``solver.info["iterations"]`` the iterations
+        of every step.  ``PDEHIP_FIXEDPOINT_BATCH=<n>`` (or ``solver.batch``) fixes the number of iterations enqueued between two reads of
+        the control block (default: the count of the step before plus one); results do not depend on it."""
+        lib, stream = self._lib, self.stream
+        eq = solver.pde
+        who = "Implicit Euler" if scheme == _abi.FIXEDPOINT_IMPLICIT else "Crank-Nicolson"
+        if solver.info.get("stochastic"):
+            msg = f"Backend `{self.name}` does not support stochastic equations with {solver.__class__.__name__}"
+            raise NotImplementedError(msg)
+        spec = erhs = None
+        try:
+            if np.dtype(state.dtype).kind == "c":
+                msg = "complex state"
+                raise NotImplementedError(msg)
+            spec = self.make_rhs_spec(eq, state)
+        except NotImplementedError as err:
+            try:
+                erhs = self.make_expression_rhs(eq, state)
+            except NotImplementedError as err2:
+                if any(c.__name__ in ("DiffusionPDE", "CahnHilliardPDE") for c in type(eq).__mro__):
+                    raise err from err2
+                raise
+        if spec is not None and spec.host_time_dependent:
+            msg = (f"Backend `{self.name}`: {solver.__class__.__name__} does not support boundary conditions given as Python functions of time "
+                   "(conditions that are expressions of time are supported)")
+            raise NotImplementedError(msg)
+        if erhs is not None and not all(p.loop_ok() for p in getattr(erhs, "parts", [erhs])):
+            msg = (f"Backend `{self.name}`: {solver.__class__.__name__} needs a right-hand side that runs inside the device loops: no integrals, no "
+                   "boundary conditions given as Python functions of time, no decomposed grids")
+            raise NotImplementedError(msg)
+        info = spec.info if spec is not None else erhs.info
+        ncomp = 1 if spec is not None else int(getattr(erhs, "ncomp", 1))
+        is_complex = bool(getattr(erhs, "complex_pairs", False))
+        comp_shape = ((ncomp // 2, 2) if is_complex else (ncomp,)) if ncomp > 1 else ()
+
+        def new_array():
+            return DeviceArray(info, comp_shape, complex_pairs=is_complex)
+
+        # the state array and two iterates rotate; rate_t for Crank-Nicolson; the slope scratch only where a sweep cannot carry the update
+        work = [new_array(), new_array(), new_array() if scheme == _abi.FIXEDPOINT_CRANK_NICOLSON else None, None]
+        nbytes = C.c_size_t(0)
+        lib.fixedpoint_ctl_bytes(info.ref, ncomp, C.byref(nbytes))
+        ctl_dev = DeviceBuffer(nbytes.value)
+        fp = _abi.FixedPoint()
+        fp.scheme, fp.maxiter, fp.maxerror2 = scheme, int(solver.maxiter), float(solver.maxerror) ** 2
+        fp.explicit_fraction = float(getattr(solver, "explicit_fraction", 0.0))
+        batch = getattr(solver, "batch", None)
+        fp.batch = int(batch if batch is not None else os.environ.get("PDEHIP_FIXEDPOINT_BATCH", "0"))
+        dt = float(solver.info["dt"])
+        solver.info["function_evaluations"] = 0
+        solver.info["iterations"] = []
+        error_cls = _convergence_error(solver)
+
+        def call(state_data: DeviceArray, t: float, nsteps: int) -> DeviceArray:
+            """``nsteps`` steps from time ``t``; returns the array that holds the new state."""
+            counts = (C.c_int32 * nsteps)()
+            fp.iterations = C.cast(counts, C.POINTER(C.c_int32))
+            fp.steps_done = 0
+            fp.evaluations = 0
+            result = C.c_void_p()
+            while True:
+                ptrs = (C.c_void_p * 4)(*[None if w is None else w.ptr for w in work])
+                if spec is not None:
+                    spec.c.t = float(t)
+                    lib.fixedpoint_run(info.ref, spec.ref, C.byref(fp), dt, nsteps, state_data.ptr, ptrs, ctl_dev.ptr, ctl_dev.nbytes, C.byref(result), stream)
+                else:
+                    passes, fixed, nfixed, _keep = erhs._loop_desc("scaled")
+                    single = ncomp == 1 and getattr(erhs, "_stage_ok", True) and not getattr(erhs, "_pass_by_pass", False)
+                    program = erhs.bc_program()
+                    lib.jit_fixedpoint_run(info.ref, passes, len(passes), fixed, nfixed, ncomp, C.byref(fp), dt, float(t), nsteps, state_data.ptr, ptrs,
+                                           ctl_dev.ptr, ctl_dev.nbytes, (1 if single else 0) | (2 if is_complex else 0),
+                                           None if program is None else program.ptr, C.byref(result), stream)
+                if fp.status != 2:
+                    break
+                work[3] = new_array()      # this right-hand side writes its slope to memory: one more array, then the same call again
+                fp.evaluations = 0
+            done = int(fp.steps_done)
+            solver.info["steps"] += done
+            solver.info["function_evaluations"] += int(fp.evaluations)
+            solver.info["iterations"].extend(counts[: done + (1 if fp.status == 1 else 0)])
+            fp.iterations = None
+            if fp.status == 1:
+                raise error_cls(f"{who} step did not converge.")      # implicit.py:106-108, crank_nicolson.py:112-113
+            for k, w in enumerate(work[:2]):
+                if result.value == w.ptr:      # the rotation ended on a work array: it becomes the caller's, by a copy
+                    lib.memcpy_d2d(state_data.ptr, w.ptr, state_data.nbytes, stream)
+            return state_data
+
+        def fixed_stepper(state_data: DeviceArray, t_start: float, t_end: float):
+            steps = max(1, round((t_end - t_start) / dt))
+            if post_step is None:
+                call(state_data, t_start, steps)
+            else:
+                for i in range(steps):
+                    t = t_start + i * dt
+                    call(state_data, t, 1)
+                    res = post_step(state_data, t)          # pde/solvers/base.py:266-272: after every step, with the time it started at
+                    if res is not state_data:
+                        lib.memcpy_d2d(state_data.ptr, res.ptr, state_data.nbytes, stream)
+            return state_data, t_start + (steps - 1) * dt + dt
+
+        fixed_stepper.keepalive = (work, ctl_dev, spec, erhs, fp)   # type: ignore[attr-defined]
+        return fixed_stepper
+
     def make_inner_stepper(self, solver, state):
         """Device-level stepper ``(state: DeviceArray, t_start, t_end) -> (DeviceArray, t_last)``.
 
@@ -627,6 +763,11 @@ class StepperMixin:
                 return arr if _hook is None else _hook(arr, t)
 
             post_step.wants_prev = True   # type: ignore[attr-defined]
+        scheme = _fixedpoint_scheme(solver)
+        if scheme is not None and self._lib.has("fixedpoint_ctl_bytes", "fixedpoint_run", "jit_fixedpoint_run"):
+            # implicit Euler / Crank-Nicolson: the fixed-point loops of the library.  (A library without them - the host library of
+            # the CPU tests - refuses the two solvers below like every solver it does not know.)
+            return self._make_fixedpoint_stepper(solver, state, scheme, post_step)
         solver_name = solver.__class__.__name__
         if solver_name == "MilsteinSolver" and add_noise is None:
             solver_name = "EulerSolver"     # a deterministic equation: the Euler steps of its base class (pde/solvers/milstein.py:29)
