@@ -55,10 +55,11 @@ from .rhs import (RhsPlanningMixin, RhsSpec, SpecRhs, _match_expression_rhs, cla
 from .evaluation import _ExpressionEvaluation  # noqa: E402,F401
 from .resident import ResidentState, _config_get, _make_synced_class  # noqa: E402,F401
 from .operators_glue import _NONLINEAR_OPERATORS, OperatorGlueMixin  # noqa: E402,F401
+from .noise_hooks import NoiseHookMixin  # noqa: E402
 from .steppers import StepperMixin  # noqa: E402
 
 
-class HipBackendMixin(OperatorGlueMixin, RhsPlanningMixin, StepperMixin):
+class HipBackendMixin(OperatorGlueMixin, RhsPlanningMixin, NoiseHookMixin, StepperMixin):
     """Implementation shared by the stand-alone and the py-pde-plugin backend classes."""
 
     implementation = "hip"

@@ -755,7 +755,7 @@ class DecomposedExpressionStepper:
     the operand of a nested operator is an intermediate field, which is exchanged like the state).  Conditions - constants, arrays,
     expressions of time / position / the field - are lowered for the box with the coordinates of the whole grid
     (``SlabMesh.slab_faces`` / ``BlockMesh.block_faces``); coordinate arrays and array-valued constants are cut to the box.  The
-    steppers are the Python-level twins of the C loops (``HipBackendMixin._make_expression_stepper``); the adaptive error is
+    steppers are those of a single device (the builders of ``pde_hip/steppers.py``); the adaptive error is
     MAX-reduced over the ranks.  Everything runs on the null stream (conditions are refreshed there): in order, no overlap - the
     fast decomposed paths are the fused Diffusion / Cahn-Hilliard loops of :class:`SlabStepper`.  Integrals over the grid are summed over
     the ranks (equal to the serial value up to rounding)."""
@@ -803,8 +803,8 @@ class DecomposedExpressionStepper:
         self.comm = create_communicator(self.lib, self.control) if exchanging else None
         # the evaluator: HipBackendMixin.make_expression_rhs with this object answering for the box (faces, arrays, layout)
         self.erhs = HipBackendMixin.make_expression_rhs(self, eq, state)
-        self.ncomp = int(getattr(self.erhs, "ncomp", 1))
-        parts = getattr(self.erhs, "parts", [self.erhs])
+        self.ncomp = self.erhs.ncomp
+        parts = self.erhs.parts
         # the exchange as the C loops read it (pdehip_exchange_t: pdehip_jit_euler_run / _rk_run / _euler_adaptive_run exchange the ghost
         # layers of a pass's operand themselves and reduce the adaptive error over the ranks - the reference jits its loops around the MPI
         # calls, pde/solvers/explicit_mpi.py:133-226); the Python-driven steppers (hooks, noise, integrals) call `self.exchange`
@@ -823,15 +823,7 @@ class DecomposedExpressionStepper:
         # reference's `sync_errors`, pde/solvers/base.py:577-590).
         desc = self._exchange_desc if os.environ.get("PDEHIP_DECOMP_LOOPS", "1") != "0" else None
         in_loops = desc is not None and any(tb is not None for part in parts for tb in part.pass_faces)
-        if hasattr(self.erhs, "parts"):
-            self.erhs.reduces_error_in_loops = in_loops
-        for part in parts:
-            part._reduce = self._sum_over_ranks if self.size > 1 else None
-            part._pass_by_pass = True
-            part._two_ok = False
-            part._exchange = self.exchange if exchanging else None
-            part._exchange_desc = desc
-            part.reduces_error_in_loops = in_loops
+        self.erhs.decompose(self.exchange if exchanging else None, desc, self._sum_over_ranks if self.size > 1 else None, in_loops)
         # every rank must run the same passes in the same order (the exchanges pair up by issue order): checked, not assumed
         plans = ["\n".join(part.plan.describe()) for part in parts]
         if any(other != plans for other in self.control.allgather(plans)):
@@ -908,8 +900,10 @@ class DecomposedExpressionStepper:
     def make_noise_step(self, eq, dt: float):
         """``add_noise(array)`` of an Euler-Maruyama step on the box of this rank - additive Gaussian white noise of constant
         variance ``eq.noise`` (one value, or one per field): ``state += sqrt(dt) * sqrt(noise / cell_volume) * dW`` with dW from the
-        device generator (``HipBackendMixin._make_noise_step``); every rank draws from its own part of the counter space, so the
+        device generator (``noise_hooks.variance_noise_step``); every rank draws from its own part of the counter space, so the
         boxes get independent noise (the reference's MPI nodes each run their own generator).  None for deterministic equations."""
+        from .noise_hooks import variance_noise_step
+
         if not getattr(eq, "is_sde", False):
             return None
         for cls in type(eq).__mro__:
@@ -921,45 +915,20 @@ class DecomposedExpressionStepper:
         if getattr(eq, "use_noise_realization", False) or not getattr(eq, "use_noise_variance", True):
             msg = "decomposed stepping supports Gaussian white noise given by its variance only"
             raise NotImplementedError(msg)
-        try:
-            noise = np.broadcast_to(np.asarray(getattr(eq, "noise", 0), dtype=float), (self.ncomp,))
-        except ValueError:
-            noise = None
-        if noise is None or (noise < 0).any():
-            msg = "decomposed stepping needs one non-negative noise variance per field"
-            raise NotImplementedError(msg)
-        cell_volume = float(np.prod(self.grid.discretization))
-        cells = int(np.prod(self.grid.shape))
-        scales = [float(np.sqrt(dt) * np.sqrt(v / cell_volume)) for v in noise]
-        rng = getattr(eq, "rng", None)
-        seed = int(self.control.broadcast(int((rng if rng is not None else np.random.default_rng()).integers(0, 2**32))))
-        counter = [0]
-        first = self.rank * self.ncomp * cells      # this rank's part of the counter space (a box never has more cells than the grid)
-
-        def add_noise(arr) -> None:
-            flat = arr.flat() if self.ncomp > 1 else None
-            for k in range(self.ncomp):
-                if scales[k] != 0:
-                    ptr = arr.ptr if flat is None else flat.component(k).ptr
-                    self.lib.add_gaussian_noise(self.info.ref, 1, ptr, scales[k], seed, counter[0], first + k * cells, self.stream)
-            counter[0] += 1
-
-        return add_noise
+        first = self.rank * self.ncomp * int(np.prod(self.grid.shape))      # this rank's part of the counter space (a box never has more cells than the grid)
+        return variance_noise_step(self.lib, self.stream, self.info, eq, self.ncomp, self.grid, dt, "decomposed stepping", first,
+                                   share_seed=lambda seed: int(self.control.broadcast(seed)))
 
     def make_stepper(self, scheme: str = "euler", dt: float = 1e-3, *, adaptive: bool = False, tolerance: float = 1e-4, dt_min: float = 1e-10,
                      dt_max: float = 1e10, post_step=None):
         """``stepper(state_array, t_start, t_end) -> (state_array, t_last)`` on the box of this rank, plus its ``info`` dict.
         ``post_step(array, t) -> array``: called after every (accepted) step, after the noise increment."""
-        from types import SimpleNamespace
-
-        from .backend import HipBackendMixin
+        from .steppers import SolverScheme, make_adaptive_stepper, make_fixed_stepper
 
         if scheme not in ("euler", "runge-kutta"):
             msg = f"decomposed stepping supports the schemes euler and runge-kutta (got {scheme})"
             raise NotImplementedError(msg)
-        solver = SimpleNamespace(pde=self.eq, adaptive=bool(adaptive), tolerance=float(tolerance), dt_min=float(dt_min), dt_max=float(dt_max),
-                                 info={"dt": float(dt), "steps": 0})
-        proxy = SimpleNamespace(grid=self.grid, dtype=self.dtype)
+        info = {"dt": float(dt), "steps": 0}
         hook = post_step
         add_noise = self.make_noise_step(self.eq, float(dt))
         if add_noise is not None:
@@ -975,10 +944,14 @@ class DecomposedExpressionStepper:
                 add_noise(arr)
                 return arr if hook is None else hook(arr, t)
 
-        solver.info["stochastic"] = add_noise is not None
-        step = HipBackendMixin._make_expression_stepper(self, solver, proxy, erhs=self.erhs, scheme=scheme, post_step=post_step,
-                                                        reduce_error=self._max_over_ranks if self.size > 1 else None)
-        return step, solver.info
+        info["stochastic"] = add_noise is not None
+        kind = SolverScheme(scheme, bool(adaptive), name=scheme)
+        if adaptive:
+            step = make_adaptive_stepper(self.lib, self.stream, self.erhs, kind, float(tolerance), float(dt_min), float(dt_max), info, post_step,
+                                         reduce_error=self._max_over_ranks if self.size > 1 else None)
+        else:
+            step = make_fixed_stepper(self.lib, self.stream, self.erhs, kind, float(dt), info, post_step)
+        return step, info
 
     def solve(self, global_valid: np.ndarray, t_range: float, dt: float | None, solver: str = "euler", *, tolerance: float = 1e-4,
               dt_min: float = 1e-10, dt_max: float = 1e10) -> tuple[np.ndarray, dict[str, Any]]:

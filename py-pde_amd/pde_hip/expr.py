@@ -25,6 +25,7 @@ from typing import Any
 import numpy as np
 
 from . import _abi
+from .rhs import RhsEvaluator
 
 MAX_EXTRA = 3
 OPERATORS = ("laplace", "gradient_squared")
@@ -529,8 +530,11 @@ def _run_rk(lib, info, loop, ncomp: int, y, ynew, work, err, dt: float, t0: floa
     return y if result.value == y.ptr else ynew
 
 
-class ExpressionRhs:
+class ExpressionRhs(RhsEvaluator):
     """Device evaluation of an :class:`ExpressionPlan` (kernels compiled lazily, cached per wrap mode)."""
+
+    has_loops = True
+    _stage_ok = True      # cleared when `pdehip_jit_apply_stage` reports that its kernels do not cover this grid / these conditions
 
     def __init__(self, backend, plan: ExpressionPlan, info, tables: dict, aux: dict | None = None):
         """``aux``: device arrays of the plan's auxiliary inputs by name (array-valued constants, cell coordinates).
@@ -570,26 +574,42 @@ class ExpressionRhs:
             self._red_dev = DeviceBuffer(8)
             self._red_host = np.zeros(1)
             self._cell_volume = float(np.prod(info.dx))
-        self._dynamic = [tb for tb in {id(tb): tb for tb in tables.values()}.values() if getattr(tb, "time_dependent", False)]
+        self._dynamic = [tb for tb in {id(tb): tb for tb in tables.values()}.values() if tb.time_dependent]
         # conditions that are not affine in the adjacent value read it from the field they are applied to: here that has to be
         # the state itself (the values of intermediate fields are not known when the conditions are refreshed)
         # ... an operator of a nested expression applies them to an INTERMEDIATE field (like the reference: `value` is the adjacent
         # value of whatever the operator acts on): those conditions are refreshed pass by pass from the pass's own input, which
         # keeps the evaluation out of the C loops and of the fused two-level sweep
-        self._reads_intermediate = any(tb is not None and getattr(tb, "reads_value", False) and p.src != "state"
+        self._reads_intermediate = any(tb is not None and tb.reads_value and p.src != "state"
                                        for p, tb in zip(plan.passes, self.pass_faces))
-        if any(getattr(tb, "reads_value", False) for tb in self._dynamic) and getattr(plan, "component", None) is not None:
+        if any(tb.reads_value for tb in self._dynamic) and getattr(plan, "component", None) is not None:
             msg = "hip backend: boundary conditions that depend non-linearly on the field, for the components of a vector field"
             raise NotImplementedError(msg)
         self._kernels: dict[tuple[int, str], tuple[C.c_void_p, list[str]]] = {}
         # decomposed grids (pde_hip/distributed.py): `_exchange(array)` fills the ghost layers towards the neighbouring ranks before a
         # pass applies operators to `array`; the passes then run one by one from Python (no fused chains, no C loops)
-        self._exchange = None
+        self._exchange = self._exchange_desc = None
         self._reduce = None
         self._pass_by_pass = False
         # two steps per sweep: the second level would need the faces at t + dt / the integrals of the intermediate level
         self._two_ok: bool | None = False if (self._dynamic or self.has_reductions) else None
         self._fused: dict[str, C.c_void_p | None] = {}
+
+    @property
+    def two_steps_possible(self) -> bool:
+        return self._two_ok is not False
+
+    @property
+    def stage_sweeps(self) -> bool:
+        return self._stage_ok and not self._pass_by_pass
+
+    def decompose(self, exchange, exchange_desc, reduce, reduces_error_in_loops: bool) -> None:
+        """Evaluate on the box of one rank of a decomposed grid: ``exchange(array)`` fills the ghost layers towards the neighbours
+        before a pass applies operators to ``array`` (``exchange_desc``: the same for the C loops, None keeps them away),
+        ``reduce(value)`` sums an integral over the ranks.  The passes run one by one, one step per sweep."""
+        self._exchange, self._exchange_desc, self._reduce = exchange, exchange_desc, reduce
+        self._pass_by_pass, self._two_ok = True, False
+        self.reduces_error_in_loops = reduces_error_in_loops
 
     def _update_faces(self, t: float, state=None) -> None:
         """Coefficient arrays of faces that depend on the time or on the field ``state`` (expression BCs, ``pde_hip/bc_expr.py``)."""
@@ -603,7 +623,7 @@ class ExpressionRhs:
     def _refresh_for_pass(self, index: int, src, t: float) -> None:
         """Conditions that read the field, applied to an intermediate field: rewritten from the input of THIS pass."""
         tb = self.pass_faces[index]
-        if self._reads_intermediate and tb is not None and getattr(tb, "reads_value", False):
+        if self._reads_intermediate and tb is not None and tb.reads_value:
             tb.update({"t": t}, state=src, stream=self.backend.stream)     # (also for passes on the state itself: an earlier pass may have rewritten a shared table)
 
     def _kernel(self, index: int, wrap: str):
@@ -666,7 +686,7 @@ class ExpressionRhs:
         update + error norm into ``err``).  Returns False when the sweep is not available - then ``k_out`` holds the slope
         (plain ``apply``) and the caller combines with the pointwise kernels.  Two-pass chains keep their fused two-level
         sweep (tmp in registers) and combine separately."""
-        if (not getattr(self, "_stage_ok", True) or self._pass_by_pass or self._fused_handle("scaled") is not None or self.has_reductions
+        if (not self.stage_sweeps or self._fused_handle("scaled") is not None or self.has_reductions
                 or self._reads_intermediate):
             self.apply(state, k_out, "scaled", dt, t)
             return False
@@ -700,9 +720,9 @@ class ExpressionRhs:
         expressions of time are refreshed on the device inside the loops: :meth:`bc_program`)."""
         # (decomposed grids - `_exchange` set -: only with the exchange descriptor the C loops read, `_exchange_desc`; the loops run the
         # passes one by one, which is all `_pass_by_pass` asks for)
-        decomposed_ok = self._exchange is None or getattr(self, "_exchange_desc", None) is not None
+        decomposed_ok = self._exchange is None or self._exchange_desc is not None
         return (not self.has_reductions and not self._reads_intermediate and decomposed_ok
-                and not any(getattr(tb, "host_only", False) for tb in self._dynamic))
+                and not any(tb.host_only for tb in self._dynamic))
 
     def bc_program(self):
         """Device program (``pde_hip.bc_expr.BcProgram``) of all time-dependent faces of this expression's tables, or None."""
@@ -748,7 +768,7 @@ class ExpressionRhs:
             keep.append(faces)
             # decomposed grids: the ghost layers of an operand travel before the FIRST pass of an evaluation that applies operators to
             # it (`exchanged`: what earlier passes - also of the other equations of a system - have exchanged already)
-            desc = getattr(self, "_exchange_desc", None)
+            desc = self._exchange_desc
             if desc is not None and self.pass_faces[i] is not None and (exchanged is None or e.src not in exchanged):
                 e.exchange = C.addressof(desc)
                 keep.append(desc)
@@ -762,10 +782,11 @@ class ExpressionRhs:
         holds the result, or None when the loop is not available (then nothing was done)."""
         if not self.loop_ok():
             return None
-        return _run_loop(self.lib, self.info, self._loop_desc("euler"), state, other, 1, dt, t0, nsteps, self.plan.uses_time, self.backend.stream,
+        return _run_loop(self.lib, self.info, self.loop_desc("euler"), state, other, 1, dt, t0, nsteps, self.plan.uses_time, self.backend.stream,
                          self.bc_program())
 
-    def _loop_desc(self, wrap: str):
+    def loop_desc(self, wrap: str):
+        """(passes, fixed pointers, their count, keep-alive) of one evaluation as the C loops take it (``pdehip_jit_pass_t``)."""
         cache = self.__dict__.setdefault("_loops", {})
         if wrap not in cache:
             fixed: list = []
@@ -784,8 +805,8 @@ class ExpressionRhs:
         chain = self._fused_handle("scaled") is not None
         if chain and int(np.prod(self.info.shape)) > (1 << 21):
             return None
-        stage_fuse = getattr(self, "_stage_ok", True) and not chain and not self._pass_by_pass
-        return _run_rk(self.lib, self.info, self._loop_desc("scaled"), 1, y, ynew, work, err, dt, t0, nsteps, ctl, stage_fuse, self.backend.stream,
+        stage_fuse = self.stage_sweeps and not chain
+        return _run_rk(self.lib, self.info, self.loop_desc("scaled"), 1, y, ynew, work, err, dt, t0, nsteps, ctl, stage_fuse, self.backend.stream,
                        self.bc_program(), euler_adaptive)
 
     def _fused_handle(self, wrap: str):
@@ -853,21 +874,24 @@ class ExpressionRhs:
                 pass
 
 
-class SystemRhs:
+class SystemRhs(RhsEvaluator):
     """Right-hand side of a multi-field ``PDE({"u": ..., "v": ...})`` whose fields are all scalar (reference:
     ``pde/pdes/pde.py:401-499`` compiles one function per variable over a ``FieldCollection``): one
     :class:`ExpressionRhs` per equation, each seeing the other fields as centre-only inputs (or, where an operator is applied
     to another field, as the stencil array of a pass).  The state is ONE device array with a leading component axis, like
-    ``FieldCollection.data``.  Same evaluator interface as :class:`ExpressionRhs`; the fused sweeps of single-field
-    expressions (two steps per sweep, stage epilogues) do not apply — stages combine with the pointwise kernels."""
+    ``FieldCollection.data``.  The fused sweeps of single-field expressions (two steps per sweep, stage epilogues) do not
+    apply — stages combine with the pointwise kernels."""
 
-    def __init__(self, variables: list[str], parts: list["ExpressionRhs"], info):
+    has_loops = True
+    parts = None     # (the evaluators of the equations: a plain attribute here)
+
+    def __init__(self, variables: list[str], parts: list["ExpressionRhs"], info, complex_pairs: bool = False):
         self.variables, self.parts, self.info = list(variables), list(parts), info
-        self.ncomp = len(self.variables)
+        self.ncomp, self.complex_pairs = len(self.variables), bool(complex_pairs)
         # conditions that read the field: an operator of one equation may act on ANOTHER field of the system - refreshed pass by
         # pass from the array the pass reads (the component views below), which keeps the system out of the C loops
         for part in self.parts:
-            if any(getattr(tb, "reads_value", False) for tb in part._dynamic):
+            if any(tb.reads_value for tb in part._dynamic):
                 part._reads_intermediate = True
 
     def apply(self, state, out, wrap: str = "rate", dt: float = 0.0, t: float = 0.0) -> None:
@@ -877,12 +901,10 @@ class SystemRhs:
             others = {n: a for n, a in comps.items() if n != name}
             part.apply(comps[name], out.component(k), wrap, dt, t, others=others)
 
-    def apply_stage(self, state, k_out, dt, t, kind, y, ks, coefs, c_new, out2, err=None) -> bool:
-        self.apply(state, k_out, "scaled", dt, t)
-        return False
-
-    def euler2(self, state, out, dt: float) -> bool:
-        return False
+    def decompose(self, exchange, exchange_desc, reduce, reduces_error_in_loops: bool) -> None:
+        self.reduces_error_in_loops = reduces_error_in_loops
+        for part in self.parts:
+            part.decompose(exchange, exchange_desc, reduce, reduces_error_in_loops)
 
     def euler_loop(self, state, other, dt: float, t0: float, nsteps: int):
         """The fixed-step Euler loop of the whole system in one C call (every equation reads the current state of all
@@ -891,10 +913,10 @@ class SystemRhs:
             return None
         part0 = self.parts[0]
         uses_time = any(p.plan.uses_time for p in self.parts)
-        return _run_loop(part0.lib, self.info, self._loop_desc("euler"), state, other, self.ncomp, dt, t0, nsteps, uses_time, part0.backend.stream,
+        return _run_loop(part0.lib, self.info, self.loop_desc("euler"), state, other, self.ncomp, dt, t0, nsteps, uses_time, part0.backend.stream,
                          self.bc_program())
 
-    def _loop_desc(self, wrap: str):
+    def loop_desc(self, wrap: str):
         cache = self.__dict__.setdefault("_loops", {})
         if wrap not in cache:
             fixed: list = []
@@ -924,6 +946,6 @@ class SystemRhs:
         part0 = self.parts[0]
         # (stage_fuse bit 1: the components are the (re, im) pairs of complex fields - modulus error norm from an explicit error field,
         # the last array of `work`)
-        pairs = 2 if (ctl is not None and getattr(self, "complex_pairs", False)) else 0
-        return _run_rk(part0.lib, self.info, self._loop_desc("scaled"), self.ncomp, y, ynew, work, err, dt, t0, nsteps, ctl, pairs,
+        pairs = 2 if (ctl is not None and self.complex_pairs) else 0
+        return _run_rk(part0.lib, self.info, self.loop_desc("scaled"), self.ncomp, y, ynew, work, err, dt, t0, nsteps, ctl, pairs,
                        part0.backend.stream, self.bc_program(), euler_adaptive)

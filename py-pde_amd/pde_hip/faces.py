@@ -7,17 +7,13 @@ Reference: ``pde/grids/boundaries/local.py:766-1150`` (``get_virtual_point_data`
 from __future__ import annotations
 
 import ctypes as C
-import inspect
 import logging
-import os
-from collections import defaultdict
-from typing import Any, Callable, NamedTuple
 
 import numpy as np
 
 from . import _abi
 from ._lib import require_device
-from .device import DeviceArray, DeviceBuffer, DeviceScalar, GridInfo, ptr_array
+from .device import DeviceArray, DeviceBuffer
 
 _logger = logging.getLogger("pde_hip.backend")
 
@@ -27,6 +23,9 @@ _logger = logging.getLogger("pde_hip.backend")
 # ---------------------------------------------------------------------------------------------
 class FaceTable:
     """ctypes face table + the device arrays it points to (kept alive with it)."""
+
+    # the protocol of all face tables (ExprFaceTable, HostSetterTable): constant coefficients need no refresh
+    time_dependent = reads_value = host_only = False
 
     def __init__(self):
         self.c = _abi.FaceArray()

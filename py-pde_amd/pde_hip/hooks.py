@@ -9,7 +9,7 @@ that expression runs as ONE run-time compiled pointwise pass per step (``pde_hip
 
 What cannot be traced - reductions (``state_data.sum()``), Python control flow on values (``if state_data.max() > 1: raise
 StopIteration``), auxiliary hook data that changes, states that are not one real scalar field - raises during the trace; the caller then
-keeps the host round trip (``HipBackendMixin._make_host_post_step``).  The trace calls the hook ONCE at set-up with the symbolic array
+keeps the host round trip (``NoiseHookMixin._make_host_post_step``, ``pde_hip/noise_hooks.py``).  The trace calls the hook ONCE at set-up with the symbolic array
 (a numba compilation does not call it at all): hooks with Python side effects see one extra call.
 """
 

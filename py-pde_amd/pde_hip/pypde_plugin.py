@@ -231,7 +231,7 @@ class HipSlabSolver(AdaptiveSolverBase):
                 raise NotImplementedError(msg)
             SlabStepper._describe(self.pde, state.grid)
         except NotImplementedError:
-            return self._make_expression_stepper(state, float(dt), device, has_hook)
+            return _decomposed_expression_stepper(self, state, float(dt), device, has_hook)
         blocks = self.decomposition != "slab"
         if blocks:
             # a decomposition that only cuts axis 0 IS the slab decomposition (always the case for 1-D grids): the slab loops take it
@@ -360,9 +360,6 @@ def _decomposed_expression_stepper(self, state, dt: float, device, has_hook: boo
 
     expression_stepper.slab = stepper  # type: ignore[attr-defined]
     return expression_stepper
-
-
-HipSlabSolver._make_expression_stepper = _decomposed_expression_stepper
 
 
 class HipConsistencyTracker(_trackers.ConsistencyTracker):

@@ -8,17 +8,14 @@ Reference: ``pde/pdes/diffusion.py:99-123``, ``pde/pdes/cahn_hilliard.py:95-124`
 from __future__ import annotations
 
 import ctypes as C
-import inspect
 import logging
-import os
-from collections import defaultdict
-from typing import Any, Callable, NamedTuple
+from typing import Any
 
 import numpy as np
 
 from . import _abi
 from ._lib import require_device
-from .device import DeviceArray, DeviceBuffer, DeviceScalar, GridInfo, ptr_array
+from .device import DeviceArray, GridInfo
 from .faces import HostSetterTable, convert_bcs, real_dtype_of
 
 _logger = logging.getLogger("pde_hip.backend")
@@ -127,10 +124,10 @@ class RhsSpec:
         # evaluation (`pdehip_rhs_t::bc_program`, `t`); faces given as Python functions stay on the host (`host_time_dependent`)
         # (... and faces that are not affine in the adjacent value: the program reads the input field of every evaluation)
         self.program = None
-        if bc_mu is not None and getattr(bc_mu, "reads_value", False):
+        if bc_mu is not None and bc_mu.reads_value:
             msg = "hip backend: conditions of the chemical potential that depend non-linearly on it (mu is never stored between the two operators)"
             raise NotImplementedError(msg)
-        if self.host_time_dependent and any(getattr(tb, "reads_value", False) for tb in (bc_c, bc_mu) if tb is not None):
+        if self.host_time_dependent and any(tb.reads_value for tb in (bc_c, bc_mu) if tb is not None):
             msg = "hip backend: conditions given as Python functions together with conditions that depend non-linearly on the field"
             raise NotImplementedError(msg)
         if self.time_dependent and not self.host_time_dependent:
@@ -143,12 +140,12 @@ class RhsSpec:
     @property
     def time_dependent(self) -> bool:
         """Faces whose coefficient arrays must be refreshed when the time changes (expression BCs with `t`)."""
-        return any(getattr(tb, "time_dependent", False) for tb in (self.bc_c, self.bc_mu) if tb is not None)
+        return any(tb.time_dependent for tb in (self.bc_c, self.bc_mu) if tb is not None)
 
     @property
     def host_time_dependent(self) -> bool:
         """... and some of them are Python functions: refreshed from the host, which keeps the steps out of the C loops."""
-        return any(getattr(tb, "host_only", False) for tb in (self.bc_c, self.bc_mu) if tb is not None)
+        return any(tb.host_only for tb in (self.bc_c, self.bc_mu) if tb is not None)
 
     def update(self, t: float, stream=None) -> None:
         """Time of the next evaluation: the C entry points refresh the device-evaluated faces themselves (``self.c.t``); faces
@@ -156,7 +153,7 @@ class RhsSpec:
         self.c.t = float(t)
         if self.program is None:
             for tb in (self.bc_c, self.bc_mu):
-                if tb is not None and getattr(tb, "time_dependent", False):
+                if tb is not None and tb.time_dependent:
                     tb.update({"t": t}, stream=stream)
 
     @property
@@ -242,13 +239,61 @@ def _match_expression_rhs(expr_str: str, var: str, consts: dict[str, Any]) -> tu
     return None
 
 
-class SpecRhs:
-    """A fused class right-hand side (:class:`RhsSpec`) behind the evaluator interface of
-    :class:`~pde_hip.expr.ExpressionRhs`, for steppers driven from Python: every evaluation first refreshes the
-    coefficient arrays of time-dependent faces (``args={"t": t}`` of the reference, ``pde/pdes/diffusion.py:119-121``)."""
+class RhsEvaluator:
+    """The interface the steppers drive (``pde_hip/steppers.py``, ``DecomposedExpressionStepper``): ``apply`` always works, every fast
+    path answers "not available" by default and the stepper then takes the general one.  Implementations: :class:`SpecRhs` (class
+    right-hand sides), :class:`~pde_hip.expr.ExpressionRhs` (one expression), :class:`~pde_hip.expr.SystemRhs` (several fields)."""
+
+    info = None                        # GridInfo of the arrays
+    ncomp = 1                          # scalar components of the state (> 1: a leading component axis)
+    complex_pairs = False              # the components are planar (re, im) pairs: modulus error norm, complex host data
+    reduces_error_in_loops = False     # decomposed grids: the C loops MAX-reduce the adaptive error over the ranks themselves
+    has_loops = False                  # `euler_loop` / `rk_run` exist (they may still answer None for a particular right-hand side)
+    two_steps_possible = False         # `euler2` may still succeed
+    stage_sweeps = False               # one sweep per stage carries the epilogue inside the C loops too (`apply_stage` kinds)
+
+    def apply(self, state, out, wrap: str = "rate", dt: float = 0.0, t: float = 0.0) -> None:
+        """out = F(state)  |  dt*F(state)  |  state + dt*F(state)   (wrap = rate | scaled | euler) at time ``t``."""
+        raise NotImplementedError
+
+    def apply_stage(self, state, k_out, dt, t, kind, y, ks, coefs, c_new, out2, err=None) -> bool:
+        """k_out = dt*F(state) and, in the same sweep, the combination that follows (see ``ExpressionRhs.apply_stage``); False: only
+        the slope was written and the caller combines with the pointwise kernels."""
+        self.apply(state, k_out, "scaled", dt, t)
+        return False
+
+    def euler2(self, state, out, dt: float) -> bool:
+        """Two Euler steps in one sweep; False: nothing done."""
+        return False
+
+    def ab2_step(self, state, out, rate, rate_prev, dt: float, t: float) -> bool:
+        """Rate (into ``rate``) and Adams-Bashforth update (into ``out``) in one sweep; False: nothing done."""
+        return False
+
+    def euler_loop(self, state, other, dt: float, t0: float, nsteps: int):
+        """``nsteps`` Euler steps in one C call; the array holding the result, or None: nothing done."""
+
+    def rk_run(self, y, ynew, work, err, dt: float, t0: float, nsteps: int, ctl=None, euler_adaptive: bool = False):
+        """RK4 steps / an adaptive loop in one C call; the array holding the result, or None: nothing done."""
+
+    def loop_ok(self) -> bool:
+        """The passes can run inside the C loops: ``loop_desc(wrap)`` describes them, ``bc_program()`` (or None) refreshes their faces."""
+        return False
+
+    def bc_program(self):
+        return None
+
+    parts = property(lambda self: [self], doc="The evaluators of the single equations.")
+
+
+class SpecRhs(RhsEvaluator):
+    """A fused class right-hand side (:class:`RhsSpec`) behind the evaluator interface, for steppers driven from Python: every
+    evaluation first refreshes the coefficient arrays of time-dependent faces (``args={"t": t}`` of the reference,
+    ``pde/pdes/diffusion.py:119-121``).  No two steps per sweep: the second level would need the faces at t + dt."""
 
     def __init__(self, backend, spec: RhsSpec):
         self.backend, self.spec, self.info, self.lib = backend, spec, spec.info, backend._lib
+        self._ab2_ok = True
 
     def apply(self, state, out, wrap: str = "rate", dt: float = 0.0, t: float = 0.0) -> None:
         spec, st = self.spec, self.backend.stream
@@ -260,12 +305,13 @@ class SpecRhs:
         else:
             self.lib.rhs_scaled(self.info.ref, spec.ref, state.ptr, out.ptr, 1.0 if wrap == "rate" else dt, st)
 
-    def apply_stage(self, state, k_out, dt, t, kind, y, ks, coefs, c_new, out2, err=None) -> bool:
-        self.apply(state, k_out, "scaled", dt, t)
-        return False   # the caller combines with the pointwise kernels
-
-    def euler2(self, state, out, dt: float) -> bool:
-        return False   # the second level would need the faces at t + dt
+    def ab2_step(self, state, out, rate, rate_prev, dt: float, t: float) -> bool:
+        if self._ab2_ok:      # (`pdehip_ab2_step` reports whether its kernels cover this grid and these conditions: asked once)
+            fused = C.c_int(0)
+            self.spec.c.t = float(t)
+            self.lib.ab2_step(self.info.ref, self.spec.ref, state.ptr, out.ptr, rate.ptr, rate_prev.ptr, dt, C.byref(fused), self.backend.stream)
+            self._ab2_ok = bool(fused.value)
+        return self._ab2_ok
 
 
 class RhsPlanningMixin:
@@ -550,6 +596,4 @@ class RhsPlanningMixin:
             return parts[0]
         from .expr import SystemRhs
 
-        system = SystemRhs(variables, parts, info)
-        system.complex_pairs = is_complex          # the state is complex: planar (re, im) pairs, modulus error norm
-        return system
+        return SystemRhs(variables, parts, info, complex_pairs=is_complex)   # (a complex state: planar (re, im) pairs, modulus error norm)
