@@ -702,6 +702,49 @@ int pdehip_jit_fixedpoint_run(const pdehip_grid_t *g, const pdehip_jit_pass_t *p
                               pdehip_fixedpoint_t *fp, double dt, double t0, int64_t nsteps, void *state_full, void *const *work4_host,
                               void *ctl_dev, size_t ctl_bytes, int stage_fuse, void *bc_program, void **result, void *stream);
 
+/* ---- Poisson's and Laplace's equation (optional entry points: the ABI version stays 8, a library without them still loads) ----
+ * The reference's one stationary solve: the operator `poisson_solver` (pde/backends/scipy/operators/cartesian.py:472-489, which builds
+ * the Laplacian with its conditions as a sparse matrix plus a constant vector, `_get_laplace_matrix`, and hands both to
+ * make_general_poisson_solver, pde/backends/scipy/operators/common.py:71-146: spsolve, else lsmr), used by solve_poisson_equation /
+ * solve_laplace_equation (pde/pdes/laplace.py:28-125).  Here: `L u = f` with L = the 3/5/7-point Laplacian of the grid and the given
+ * faces, split like the reference into L u = A u + v (A: every face with its constant dropped; v = L(0)) and solved as
+ * (-A) u = v - f by conjugate gradients ON THE DEVICE, single-reduction form (Chronopoulos-Gear): per iteration one stencil sweep
+ * w = -A r that also leaves every wave's share of r.r and r.w (poisson_apply_kernel behind the ghost kernel; fp64 partial sums in fixed
+ * slots, no atomics), a one-workgroup kernel (sums in a fixed order, alpha, beta, stop test `||r|| <= max(rtol * ||f - v||, atol)`, control
+ * block) and one pointwise sweep (p, q, x, r).  The host enqueues `batch` iterations, whose launches return at entry once the solve
+ * is over, and reads the 128-byte control block through pinned memory once per batch; results do not depend on the batch size and
+ * two runs give equal bits.  Fields fp64 or fp32; work vectors and scalars are fp64 either way.
+ *
+ * Faces: first-order conditions whose virtual point comes from the adjacent cell (Dirichlet, Neumann, mixed / Robin; scalar or
+ * PDEHIP_BCF_ARRAYS coefficients) or periodic axes - they keep A symmetric.  Second-order faces (`index2`), PDEHIP_BC_SKIP and
+ * PDEHIP_BCF_NORMAL are refused (PDEHIP_E_NOTIMPL, the message names the face).  Coefficient arrays are read at every solve, so a
+ * bc program may rewrite them between solves; whether the system is singular is decided in pdehip_poisson_create.
+ *
+ * Singular systems (every face periodic or Neumann, i.e. factor1 == 1 everywhere): the reference falls through spsolve's
+ * MatrixRankWarning to lsmr - the minimum-norm least-squares solution - and raises unless `A x` is allclose to the right-hand side
+ * (common.py:112-141).  Here the mean of the right-hand side is projected out, the iterates start from 0, the mean of x is removed
+ * at the end, and one more sweep counts the cells with |A x - (f - v)| > 1e-5 + 1e-5 |f - v|: status 4 if there are any.
+ *
+ * The handle owns the five work vectors (x, r, p, q, w), the slots, the control block and its pinned mirror; it serves any number of
+ * right-hand sides.  `rhs_full` and `out_full` are full arrays of the grid (only interior cells are read / written; they may be the
+ * same array). */
+typedef struct pdehip_poisson {
+    double rtol, atol;           /* in: stop at ||r||_2 <= max(rtol * ||f - v||_2, atol) */
+    int32_t maxiter;             /* in: >= 1, updates of x at most */
+    int32_t batch;               /* in: iterations enqueued between two reads of the control block; 0: 32 */
+    int32_t iterations;          /* out: updates of x done */
+    int32_t status;              /* out: 0 converged, 1 maxiter updates without convergence, 2 a non-finite scalar, 3 breakdown (r.Ar or p.Ap
+                                    not positive: the system is not definite), 4 singular system whose solution fails the reference's test */
+    double residual;             /* out: ||r||_2 of the last iterate (the recurrence's residual) */
+    double rhs_norm;             /* out: ||f - v||_2 (singular systems: after the projection) */
+    double check_residual;       /* out: singular systems: ||A x - (f - v)||_2 of the final test (common.py:135) */
+    int32_t singular;            /* out: 1 = the system was treated as singular */
+    int32_t reserved;
+} pdehip_poisson_t;
+int pdehip_poisson_create(const pdehip_grid_t *g, const pdehip_bc_face_t *faces, void **handle);
+int pdehip_poisson_solve(void *handle, const void *rhs_full, void *out_full, pdehip_poisson_t *io, void *stream);
+int pdehip_poisson_destroy(void *handle);
+
 #ifdef __cplusplus
 }
 #endif

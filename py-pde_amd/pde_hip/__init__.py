@@ -21,6 +21,7 @@ from .fields import FieldCollection, ScalarField, Tensor2Field, VectorField
 from .grids import CartesianGrid, UnitGrid
 from .pdes import (PDE, AllenCahnPDE, CahnHilliardPDE, DiffusionPDE, KleinGordonPDE, KPZInterfacePDE, KuramotoSivashinskyPDE,
                    SwiftHohenbergPDE, WavePDE)
+from .poisson import solve_laplace_equation, solve_poisson_equation
 from .solvers import Controller, ConvergenceError, CrankNicolsonSolver, EulerSolver, ExplicitSolver, ImplicitSolver, RungeKuttaSolver
 
 _operators.register_all(HipBackend, CartesianGrid)
@@ -51,5 +52,7 @@ __all__ = [
     "UnitGrid",
     "VectorField",
     "get_backend",
+    "solve_laplace_equation",
+    "solve_poisson_equation",
 ]
 __version__ = "0.1.0"

@@ -143,6 +143,27 @@ class FixedPoint(C.Structure):
 FIXEDPOINT_IMPLICIT, FIXEDPOINT_CRANK_NICOLSON = 0, 1
 
 
+class Poisson(C.Structure):
+    """``pdehip_poisson_t``: parameters and results of one conjugate-gradient solve (``pdehip_poisson_solve``)."""
+
+    _fields_ = [
+        ("rtol", C.c_double),
+        ("atol", C.c_double),
+        ("maxiter", C.c_int32),
+        ("batch", C.c_int32),
+        ("iterations", C.c_int32),
+        ("status", C.c_int32),
+        ("residual", C.c_double),
+        ("rhs_norm", C.c_double),
+        ("check_residual", C.c_double),
+        ("singular", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
+POISSON_CONVERGED, POISSON_MAXITER, POISSON_NONFINITE, POISSON_BREAKDOWN, POISSON_INCONSISTENT = 0, 1, 2, 3, 4
+
+
 def adaptive_statistics(ctl: Adaptive) -> dict:
     """Statistics of the accepted step sizes in the format of ``OnlineStatistics.to_dict`` (pde/tools/math.py:125-174)."""
     import math
@@ -311,6 +332,10 @@ OPTIONAL_PROTOTYPES: dict[str, list] = {
     "fixedpoint_ctl_bytes": [_pg, _i, C.POINTER(C.c_size_t)],
     "fixedpoint_run": [_pg, _pr, _pfp, _d, _i64, _vp, _pvp, _vp, C.c_size_t, _pvp, _vp],
     "jit_fixedpoint_run": [_pg, C.POINTER(JitPass), _i, _pvp, _i, _i, _pfp, _d, _d, _i64, _vp, _pvp, _vp, C.c_size_t, _i, _vp, _pvp, _vp],
+    # Poisson's / Laplace's equation by conjugate gradients on the device (optional additions: the ABI version stays 8)
+    "poisson_create": [_pg, _pf, _pvp],
+    "poisson_solve": [_vp, _vp, _vp, C.POINTER(Poisson), _vp],
+    "poisson_destroy": [_vp],
 }
 
 

@@ -165,3 +165,7 @@ def register_all(backend_cls, grid_cls) -> None:
     reg(grid_cls, "vector_gradient", make_vector_gradient, rank_in=1, rank_out=2)
     reg(grid_cls, "vector_laplace", make_vector_laplace, rank_in=1, rank_out=1)
     reg(grid_cls, "tensor_divergence", make_tensor_divergence, rank_in=2, rank_out=1)
+    # the one operator that is made of its boundary conditions (pde_hip/poisson.py; the reference registers it with its scipy backend only)
+    from .poisson import make_poisson_solver
+
+    reg(grid_cls, "poisson_solver", make_poisson_solver, rank_in=0, rank_out=0)

@@ -127,6 +127,7 @@ class OperatorGlueMixin:
     def make_operator_no_bc(self, grid, operator, *, dtype=None, **kwargs):
         """``impl(arr_full: DeviceArray, out: DeviceArray)``; ghost cells are the caller's job."""
         info = self.get_operator_info(grid, operator)
+        kwargs.pop("bcs", None)      # (operators made of their conditions say themselves that they need `make_operator`)
         return info.factory(grid, backend=self, **kwargs)
 
     def _apply_operator(self, func, *values: np.ndarray, out: np.ndarray, grid=None, **kwargs) -> None:
@@ -174,6 +175,9 @@ class OperatorGlueMixin:
         is returned.
         """
         info = self.get_operator_info(grid, operator)
+        if getattr(info.factory, "_hip_needs_bcs", False):
+            # `poisson_solver`: the conditions are part of the operator (the reference's `factory(bcs=...)`, pde/pdes/laplace.py:79)
+            return info.factory(grid, backend=self, bcs=bcs, dtype=dtype, **kwargs)
         op_no_bc = info.factory(grid, backend=self, **kwargs)
         nd = len(grid.shape)
         shape_in = (grid.dim,) * info.rank_in + tuple(grid.shape)
