@@ -441,12 +441,19 @@ int pdehip_slab_euler2_run(void *comm, const pdehip_grid_t *g_local, const pdehi
  * neighbours): freed here (after the runs that use them), allocated again on demand.  A communicator frees its own in pdehip_comm_destroy.
  * (ABI version 7; the reference has no counterpart: numpy arrays are garbage-collected.) */
 int pdehip_release_scratch(void);
-/* Communication-avoiding variant (ABI version 7): FOUR halo layers per side, ONE exchange per FOUR steps (two two-step sweeps; the first
- * computes the own layers and two more per exchanged side, the second the own layers).  The part of the first sweep that reads own cells only
- * runs while the exchange of the group before is in flight; the boundary part waits for it - all sweeps on ONE stream, the halo stream
- * carries ncclSend / ncclRecv only.  Same arithmetic, bit-identical results.  Replaces the blocking per-step exchange of
- * pde/solvers/explicit_mpi.py:133-226 + pde/backends/numba_mpi/backend.py:163-194.  Same contract and preconditions as
- * pdehip_slab_euler2_run, with >= 8 local layers on EVERY rank (the caller checks globally) and *ok != 0 from pdehip_slab_euler4_supported. */
+/* Communication-avoiding variant (ABI version 7): FOUR halo layers per side, ONE exchange per FOUR steps (two two-step sweeps per group).
+ * Default schedule (3; PDEHIP_SLAB_DEEP_MODE = 1..4 selects another, read per call): FOUR private arrays with four halo layers per side -
+ * three state arrays in rotation (cur -> mid -> nxt) and one scratch array.  The compute stream runs the two interior sweeps of a group
+ * (the layers that read own cells only); the halo stream computes the four boundary layers per exchanged side of `nxt` a whole group
+ * ahead - straight from `cur` and its halos, in two short two-step passes through the scratch array - and sends / receives them, so the
+ * exchange and the boundary work stay off the critical path and the two chains meet once per group.  Schedule 4: the second boundary pass
+ * reads what the first interior sweep produced instead of recomputing it.  Schedules 1 and 2 (two private arrays): every sweep on ONE
+ * stream, the first sweep of a group computes two layers more per exchanged side and is cut into an interior launch, which runs while the
+ * exchange of the group before is in flight, and a boundary launch that waits for it (2: the second sweep is cut too); the halo stream
+ * carries ncclSend / ncclRecv only.  Every schedule computes each cell from the same inputs in the same order: bit-identical results.
+ * Replaces the blocking per-step exchange of pde/solvers/explicit_mpi.py:133-226 + pde/backends/numba_mpi/backend.py:163-194.  Same
+ * contract and preconditions as pdehip_slab_euler2_run, with >= 8 local layers on EVERY rank (the caller checks globally) and *ok != 0
+ * from pdehip_slab_euler4_supported. */
 int pdehip_slab_euler4_supported(const pdehip_grid_t *g_local, const pdehip_rhs_t *rhs, int *ok);
 int pdehip_slab_euler4_run(void *comm, const pdehip_grid_t *g_local, const pdehip_rhs_t *rhs, int lower,
                            int upper, void *buf_a, void *buf_b, double dt, int64_t nsteps, void **result,

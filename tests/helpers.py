@@ -8,6 +8,7 @@ from pathlib import Path
 import numpy as np
 
 import pde_hip
+from oracle import pde_oracle as O
 from pde_hip import _abi
 from pde_hip.backend import convert_bcs
 
@@ -75,3 +76,18 @@ def max_rel(a: np.ndarray, b: np.ndarray) -> float:
     """The parity metric of BASELINE.md §3: max|a-b| / max|b|."""
     denom = np.abs(b).max()
     return float(np.abs(a - b).max() / (denom if denom > 0 else 1.0))
+
+
+def expect_steps(eq_kind, param, grid, bc, data, dt, steps, solver="euler"):
+    """`steps` fixed Euler / RK4 steps of the CPU oracle on the whole grid, in the type of `data`; returns the valid cells."""
+    g = oracle_grid(grid, data.dtype)
+    hf = host_faces(grid.get_boundary_conditions(bc))
+    scratch = np.zeros(grid._shape_full, data.dtype)
+    rhs = O.make_rhs(eq_kind, param, hf.c, hf.c, scratch)
+    y = to_full(grid, data)
+    if solver == "euler":
+        y = O.euler_run(g, rhs, y, dt, steps)
+    else:
+        for _ in range(steps):
+            O.rk4_step(g, rhs, y, dt)
+    return interior(grid, y)

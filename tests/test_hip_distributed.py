@@ -13,6 +13,7 @@ import ctypes as C
 
 import numpy as np
 import pytest
+from helpers import expect_steps as _expect
 from helpers import host_faces, interior, max_rel, oracle_grid, to_full
 from test_oracle_golden import oracle_solve
 
@@ -21,20 +22,6 @@ from oracle import pde_oracle as O
 from pde_hip import _abi
 
 pytestmark = pytest.mark.gpu
-
-
-def _expect(eq_kind, param, grid, bc, data, dt, steps, solver="euler"):
-    g = oracle_grid(grid)
-    hf = host_faces(grid.get_boundary_conditions(bc))
-    scratch = np.zeros(grid._shape_full)
-    rhs = O.make_rhs(eq_kind, param, hf.c, hf.c, scratch)
-    y = to_full(grid, data)
-    if solver == "euler":
-        y = O.euler_run(g, rhs, y, dt, steps)
-    else:
-        for _ in range(steps):
-            O.rk4_step(g, rhs, y, dt)
-    return interior(grid, y)
 
 
 @pytest.mark.parametrize("force", [True, False])
