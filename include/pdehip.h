@@ -752,6 +752,39 @@ int pdehip_poisson_create(const pdehip_grid_t *g, const pdehip_bc_face_t *faces,
 int pdehip_poisson_solve(void *handle, const void *rhs_full, void *out_full, pdehip_poisson_t *io, void *stream);
 int pdehip_poisson_destroy(void *handle);
 
+/* The multigrid preconditioner of the same solve (optional entry points as well; the ABI version stays 8).  Plain conjugate gradients need
+ * a number of iterations proportional to the extent of the grid; with one geometric V-cycle `z = M r` per iteration the count no
+ * longer depends on it.  pdehip_poisson_set_multigrid builds the hierarchy on a handle (`opts` = NULL drops it); pdehip_poisson_solve
+ * on a handle with a hierarchy runs the PRECONDITIONED single-reduction loop: z = M r, w = -A z with the shares of r.z, z.w and r.r
+ * in the sweep, beta = r.z / (r.z)_prev, alpha = r.z / (z.w - beta r.z / alpha_prev), p = z + beta p, q = w + beta q, x += alpha p,
+ * r -= alpha q.  The stop rule is the one of the plain loop, on the true residual norm sqrt(r.r): `rtol` means the same thing for
+ * both.  Status, singular systems, batches and bit-reproducibility as above.
+ *
+ * The cycle: level l+1 halves every axis of level l whose extent is even and >= 4 (the other axes keep extent and spacing) until no
+ * axis qualifies, a level has <= 512 cells, or `max_levels` levels exist.  Every level carries the rediscretised Laplacian with the
+ * same homogeneous faces (coefficient arrays averaged over the children of each coarse face cell, once, in this call: rebuild the
+ * hierarchy when a bc program has rewritten them).  Smoother: damped Jacobi with the exact diagonal, `smooth` sweeps before and after
+ * the coarse-grid correction, `coarse_sweeps` sweeps from zero on the last level (in LDS, one workgroup, when it has <= 1024 cells).
+ * Restriction = mean of the children, prolongation = copy to the children.  M is symmetric and positive definite.
+ * LIMIT: an odd extent stops the coarsening of its axis (513^3 has one level, 500 x 500 x 300 ends at 125 x 125 x 75); the cycle is
+ * then a weaker preconditioner and the sweeps of a large last level run one launch each - correct, but slower.
+ * MEMORY: level 0 adds one work vector to the five of the handle, every further level three vectors of its size - in 3-D about
+ * 3/7 of a work vector in all - and three partial sums per wave. */
+#define PDEHIP_MG_MAX_LEVELS 32
+typedef struct pdehip_poisson_mg {
+    int32_t smooth;              /* in: Jacobi sweeps before and after the coarse-grid correction; 0: 2.  out: the value used */
+    int32_t coarse_sweeps;       /* in: sweeps from zero on the last level; 0: 32.  out: the value used */
+    int32_t max_levels;          /* in: levels at most; 0: as many as the rule above gives */
+    int32_t levels;              /* out: levels built (1: the grid does not coarsen - the cycle is `coarse_sweeps` Jacobi sweeps) */
+    double omega;                /* in: damping of the smoother; 0: 2/3, 4/5, 6/7 in 1, 2, 3 dimensions.  out: the value used */
+    int64_t shapes[PDEHIP_MG_MAX_LEVELS][PDEHIP_MAX_DIM];   /* out: extents of every level along the grid's axes */
+    uint64_t bytes;              /* out: device memory the hierarchy allocated */
+} pdehip_poisson_mg_t;
+int pdehip_poisson_set_multigrid(void *handle, pdehip_poisson_mg_t *opts);
+/* One application z = M r of the cycle on two full fp64 arrays of the grid (interior cells of r_full are read, all of z_full is
+ * written; they may be the same array).  Uses the work vectors of the handle: not while a solve on it is in flight. */
+int pdehip_poisson_precondition(void *handle, const void *r_full, void *z_full, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -70,6 +70,8 @@ __device__ __forceinline__ void poisson_wave_partial(double *ctl, double s_rr, d
     }
 }
 
+struct PoissonMg;   // pdehip_poisson_mg.hip: the hierarchy of the multigrid preconditioner
+
 struct PoissonHandle {
     pdehip_grid_t g;       // the grid of the fields handed to pdehip_poisson_solve
     pdehip_grid_t g64;     // the same grid in fp64: layout of the work vectors
@@ -83,6 +85,7 @@ struct PoissonHandle {
     int capacity = 0;
     PoissonCtl *pinned = nullptr;
     bool singular = false;         // every face periodic or Neumann: A has the constants in its null space
+    PoissonMg *mg = nullptr;       // pdehip_poisson_set_multigrid: the solve runs the preconditioned loop (pdehip_poisson_mg.h)
 };
 
 }  // namespace pdehip

@@ -1,7 +1,7 @@
 // pdehip_poisson.hip — Poisson's and Laplace's equation on the device by conjugate gradients (see pdehip_poisson.h): the handle, the
 // one-workgroup kernel behind every sweep 1 (both dot products in a fixed order, alpha / beta, stop test), the pointwise sweep 2, the
 // start (right-hand side of the split system, projection of singular systems) and the end (mean of x, the reference's `allclose` test).
-#include "pdehip_poisson.h"
+#include "pdehip_poisson_mg.h"
 
 namespace pdehip {
 
@@ -272,6 +272,7 @@ int poisson_read(PoissonHandle *h, PoissonCtl *host, void *st)
 void poisson_release(PoissonHandle *h)
 {
     if (!h) return;
+    poisson_mg_release(h);
     void *dev[] = {h->zero_face, h->x, h->r, h->p, h->q, h->w, h->ctl};
     for (void *d : dev)
         if (d) (void)hipFree(d);
@@ -333,6 +334,7 @@ int poisson_solve_t(PoissonHandle *h, const T *rhs, T *out, pdehip_poisson_t *io
     while (true) {
         const long nbatch = batch < most - enq ? batch : most - enq;
         for (long b = 0; b < nbatch; b++, enq++) {
+            if (h->mg) { PDEHIP_TRY(poisson_mg_iteration(h, st)); continue; }   // the preconditioned loop: same control block, same stop rule
             PDEHIP_TRY(poisson_sweep1(h, st));
             hipLaunchKernelGGL(poisson_finish_kernel, dim3(1), dim3(256), 0, s, ctl);
             PDEHIP_TRY(poisson_sweep2(h, st));
@@ -366,7 +368,8 @@ int poisson_solve_t(PoissonHandle *h, const T *rhs, T *out, pdehip_poisson_t *io
     }
     hipLaunchKernelGGL((poisson_store_kernel<T>), dim3(nb), dim3(256), 0, s, pg, h->x, out);
     PDEHIP_HIP(hipGetLastError());
-    note_kernel("poisson_apply_kernel<%d> (w = -A r with the wave sums of r.r and r.w in the sweep)", pg.n2 % 2 == 0 ? 2 : 1);
+    if (h->mg) poisson_mg_note(h);
+    else note_kernel("poisson_apply_kernel<%d> (w = -A r with the wave sums of r.r and r.w in the sweep)", pg.n2 % 2 == 0 ? 2 : 1);
     return 0;
 }
 

@@ -161,6 +161,23 @@ class Poisson(C.Structure):
     ]
 
 
+MG_MAX_LEVELS = 32
+
+
+class PoissonMg(C.Structure):
+    """``pdehip_poisson_mg_t``: options and description of the multigrid hierarchy of a Poisson handle (``pdehip_poisson_set_multigrid``)."""
+
+    _fields_ = [
+        ("smooth", C.c_int32),
+        ("coarse_sweeps", C.c_int32),
+        ("max_levels", C.c_int32),
+        ("levels", C.c_int32),
+        ("omega", C.c_double),
+        ("shapes", (C.c_int64 * MAX_DIM) * MG_MAX_LEVELS),
+        ("bytes", C.c_uint64),
+    ]
+
+
 POISSON_CONVERGED, POISSON_MAXITER, POISSON_NONFINITE, POISSON_BREAKDOWN, POISSON_INCONSISTENT = 0, 1, 2, 3, 4
 
 
@@ -336,6 +353,9 @@ OPTIONAL_PROTOTYPES: dict[str, list] = {
     "poisson_create": [_pg, _pf, _pvp],
     "poisson_solve": [_vp, _vp, _vp, C.POINTER(Poisson), _vp],
     "poisson_destroy": [_vp],
+    # ... preconditioned by a multigrid V-cycle (method "mgcg")
+    "poisson_set_multigrid": [_vp, C.POINTER(PoissonMg)],
+    "poisson_precondition": [_vp, _vp, _vp, _vp],
 }
 
 

@@ -6,6 +6,9 @@ plus a constant vector), ``pde/backends/scipy/operators/common.py:71-146`` (spso
 result), ``pde/pdes/laplace.py:28-125`` (the two functions).  Here the same split system is solved by conjugate gradients in
 ``libpdehip`` (``pdehip_poisson_create`` / ``_solve`` / ``_destroy``, csrc/pdehip_poisson.h); this module decides on the host what
 the loop is allowed to see - which conditions keep the matrix symmetric - and turns its status into the reference's exceptions.
+
+``method="mgcg"`` preconditions the same loop with one geometric multigrid V-cycle per iteration (``pdehip_poisson_set_multigrid``,
+csrc/pdehip_poisson_mg.h): the iteration count no longer grows with the extent of the grid.  ``"auto"`` and ``"cg"`` are the plain loop.
 """
 
 from __future__ import annotations
@@ -18,13 +21,16 @@ from . import _abi
 from .device import DeviceArray
 
 ENTRY_POINTS = ("poisson_create", "poisson_solve", "poisson_destroy")
-METHODS = ("auto", "cg")
+MG_ENTRY_POINTS = ("poisson_set_multigrid", "poisson_precondition")
+METHODS = ("auto", "cg", "mgcg")
+MG_DEFAULTS = {"mg_smooth": 2, "mg_coarse": 32, "mg_levels": None}
+MG_MAXITER = 200
 DEFAULT_RTOL = 1e-10
 DEFAULT_BATCH = 32
 
 
 def check_method(method: str) -> None:
-    """``method`` of the operator: "auto" or "cg" (the reference: "auto" or "scipy", same message, common.py:95-97)."""
+    """``method`` of the operator: "auto", "cg" or "mgcg" (the reference: "auto" or "scipy", same message, common.py:95-97)."""
     if method not in METHODS:
         msg = f"Method {method} is not available"
         raise ValueError(msg)
@@ -34,6 +40,26 @@ def default_maxiter(shape) -> int:
     """50 x the largest extent, at least 1000: conjugate gradients without a preconditioner need on the order of the extent times
     the number of digits."""
     return max(1000, 50 * max(int(n) for n in shape))
+
+
+def mg_options(method: str, kwargs: dict) -> dict:
+    """The arguments of the multigrid cycle taken out of ``kwargs`` (``mg_smooth``, ``mg_coarse``, ``mg_levels``): valid with
+    ``method="mgcg"`` only, positive integers (``mg_levels=None``: as many levels as the grid allows).  No device is touched."""
+    given = {k: kwargs.pop(k) for k in list(kwargs) if k in MG_DEFAULTS}
+    if method != "mgcg":
+        if given:
+            msg = f"poisson_solver: argument(s) {sorted(given)} need method=\"mgcg\" (method is {method!r})"
+            raise TypeError(msg)
+        return {}
+    opts = dict(MG_DEFAULTS, **given)
+    for name, value in opts.items():
+        if value is None and name == "mg_levels":
+            continue
+        if isinstance(value, bool) or int(value) != value or int(value) < 1:
+            msg = f"poisson_solver: {name} must be a positive integer (got {value!r})"
+            raise ValueError(msg)
+        opts[name] = int(value)
+    return opts
 
 
 def _face_name(axis: int, upper: bool) -> str:
@@ -99,8 +125,9 @@ def check_conditions(bcs) -> None:
 class _Solver:
     """One split system (grid, face table): the handle of the library, created at the first solve and kept for later right-hand sides."""
 
-    def __init__(self, backend, grid, table, params: dict):
+    def __init__(self, backend, grid, table, params: dict, mg: dict | None = None):
         self.backend, self.grid, self.table, self.params = backend, grid, table, params
+        self.mg, self.hierarchy = mg, {}      # mg: the options of the multigrid cycle (method "mgcg"), None: the plain loop
         self._handles: dict[str, int] = {}
         if getattr(table, "reads_value", False):
             msg = "poisson_solver: a condition is not affine in the adjacent value: the problem is not linear"
@@ -115,7 +142,20 @@ class _Solver:
             handle = C.c_void_p()
             lib.poisson_create(info.ref, self.table.c, C.byref(handle))
             self._handles[key] = handle.value
+            if self.mg is not None:
+                opts = _abi.PoissonMg()
+                opts.smooth, opts.coarse_sweeps, opts.max_levels = self.mg["mg_smooth"], self.mg["mg_coarse"], self.mg["mg_levels"] or 0
+                lib.poisson_set_multigrid(handle.value, C.byref(opts))
+                ndim = len(self.grid.shape)
+                self.hierarchy = {"levels": int(opts.levels), "level_shapes": [tuple(int(opts.shapes[lv][a]) for a in range(ndim)) for lv in range(opts.levels)],
+                                  "bytes": int(opts.bytes), "omega": float(opts.omega)}
         return self._handles[key]
+
+    def precondition(self, r: DeviceArray, z: DeviceArray) -> DeviceArray:
+        """``z = M r``: one application of the multigrid cycle to an fp64 array of the grid (tests of the cycle on its own)."""
+        lib = self.backend._lib
+        lib.poisson_precondition(self._handle(lib, r.info), r.ptr, z.ptr, self.backend.stream)
+        return z
 
     def release(self) -> None:
         handles, self._handles = self._handles, {}
@@ -141,7 +181,7 @@ class _Solver:
                 "singular": bool(io.singular), "check_residual": float(io.check_residual)}
 
 
-def raise_for_status(info: dict, maxiter: int) -> None:
+def raise_for_status(info: dict, maxiter: int, method: str = "cg") -> None:
     """The status of a solve as the exception a caller of the reference would see."""
     status = info["status"]
     if status == _abi.POISSON_CONVERGED:
@@ -149,7 +189,8 @@ def raise_for_status(info: dict, maxiter: int) -> None:
     if status == _abi.POISSON_MAXITER:
         from .solvers import ConvergenceError
 
-        msg = f"Conjugate gradients did not converge within {maxiter} iterations (residual {info['residual']:g}, right-hand side {info['rhs_norm']:g})"
+        name = "Multigrid-preconditioned conjugate gradients (mgcg)" if method == "mgcg" else "Conjugate gradients"
+        msg = f"{name} did not converge within {maxiter} iterations (residual {info['residual']:g}, right-hand side {info['rhs_norm']:g})"
         raise ConvergenceError(msg)
     if status == _abi.POISSON_INCONSISTENT:
         msg = f"Poisson problem could not be solved (Residual: {info['check_residual']})"       # common.py:135-137
@@ -165,18 +206,23 @@ def make_poisson_operator(backend, grid, bcs, dtype=None, *, method: str = "auto
     """``op(arr, out=None, args=None) -> out`` solving ``laplace(out) = arr`` with the conditions ``bcs`` (cartesian.py:472-489).
 
     ``arr``: host valid data (real or complex; host data is returned) or a :class:`DeviceArray` (a :class:`DeviceArray` is returned).
-    ``op.info`` holds iterations, residual norm, norm of the right-hand side and the convergence flag of the last call."""
+    ``op.info`` holds the method, iterations, residual norm, norm of the right-hand side and the convergence flag of the last call.
+
+    ``method="mgcg"``: conjugate gradients preconditioned by a multigrid V-cycle, with ``mg_smooth`` Jacobi sweeps before and after
+    the coarse-grid correction (default 2), ``mg_coarse`` sweeps on the last level (32) and at most ``mg_levels`` levels (None: all);
+    ``maxiter`` defaults to 200 and ``op.info`` also holds ``levels`` and ``level_shapes``.  Axes of odd extent stop coarsening."""
     from .bc_expr import convert_bcs_with_expressions, expression_faces
     from .faces import convert_bcs, real_dtype_of
 
     check_method(method)
+    mg = mg_options(method, kwargs) or None      # the options of the cycle, None for the plain loop
     if kwargs:
         msg = f"poisson_solver: unknown argument(s) {sorted(kwargs)}"
         raise TypeError(msg)
     if not (float(rtol) >= 0 and float(atol) >= 0):
         msg = "poisson_solver: rtol and atol must not be negative"
         raise ValueError(msg)
-    params = {"rtol": float(rtol), "atol": float(atol), "maxiter": default_maxiter(grid.shape) if maxiter is None else int(maxiter),
+    params = {"rtol": float(rtol), "atol": float(atol), "maxiter": (MG_MAXITER if mg else default_maxiter(grid.shape)) if maxiter is None else int(maxiter),
               "batch": DEFAULT_BATCH if batch is None else int(batch)}
     if params["maxiter"] < 1 or params["batch"] < 1:
         msg = "poisson_solver: maxiter and batch must be positive"
@@ -186,6 +232,10 @@ def make_poisson_operator(backend, grid, bcs, dtype=None, *, method: str = "auto
     if not lib.has(*ENTRY_POINTS):
         missing = sorted("pdehip_" + name for name in ENTRY_POINTS if name in lib.missing)
         msg = f"hip backend: the loaded library does not export {', '.join(missing)}: no `poisson_solver` with it"
+        raise NotImplementedError(msg)
+    if mg and not lib.has(*MG_ENTRY_POINTS):
+        missing = sorted("pdehip_" + name for name in MG_ENTRY_POINTS if name in lib.missing)
+        msg = f"hip backend: the loaded library does not export {', '.join(missing)}: no `poisson_solver` with method=\"mgcg\" with it"
         raise NotImplementedError(msg)
     check_conditions(bcs)
     has_expr = bool(expression_faces(bcs))
@@ -197,7 +247,7 @@ def make_poisson_operator(backend, grid, bcs, dtype=None, *, method: str = "auto
 
     def solver_for(part) -> _Solver:
         if part not in solvers:
-            solvers[part] = _Solver(backend, grid, table_for(part), params)
+            solvers[part] = _Solver(backend, grid, table_for(part), params, mg)
         return solvers[part]
 
     if dtype is None or np.dtype(dtype).kind != "c":
@@ -205,8 +255,11 @@ def make_poisson_operator(backend, grid, bcs, dtype=None, *, method: str = "auto
     shape = tuple(grid.shape)
 
     def fail(info: dict) -> None:
-        solve_poisson.info = {k: info[k] for k in ("iterations", "residual", "rhs_norm", "converged")}
-        raise_for_status(info, params["maxiter"])
+        solve_poisson.info = {"method": method, **{k: info[k] for k in ("iterations", "residual", "rhs_norm", "converged")}}
+        if mg:
+            hierarchy = next(iter(solvers.values())).hierarchy
+            solve_poisson.info.update(levels=hierarchy["levels"], level_shapes=hierarchy["level_shapes"])
+        raise_for_status(info, params["maxiter"], method)
 
     def solve_poisson(arr, out=None, args=None):
         host = not isinstance(arr, DeviceArray)
@@ -251,6 +304,7 @@ def make_poisson_operator(backend, grid, bcs, dtype=None, *, method: str = "auto
             return out
         return res.get_valid(out=out, stream=backend.stream)
 
+    solve_poisson.solver_for = solver_for  # type: ignore[attr-defined]
     solve_poisson.grid = grid  # type: ignore[attr-defined]
     solve_poisson.info = {}  # type: ignore[attr-defined]
     solve_poisson._hip_operator = ("poisson_solver", 0, 0)  # type: ignore[attr-defined]
@@ -276,7 +330,7 @@ make_poisson_solver._hip_needs_bcs = True  # type: ignore[attr-defined]
 # ---------------------------------------------------------------------------------------------
 def solve_poisson_equation(rhs, bc, *, label: str = "Solution to Poisson's equation", backend="hip", **kwargs):
     """Solve ``laplace(u) = rhs`` with the conditions ``bc`` (pde/pdes/laplace.py:28-97; ``kwargs``: ``method``, ``rtol``, ``atol``,
-    ``maxiter``, ``batch``).  With periodic or Neumann conditions only, the right-hand side has to be compatible with them (its
+    ``maxiter``, ``batch`` and, with ``method="mgcg"``, ``mg_smooth``, ``mg_coarse``, ``mg_levels``).  With periodic or Neumann conditions only, the right-hand side has to be compatible with them (its
     integral equals the prescribed flux): otherwise a ``RuntimeError`` with the reference's hint is raised."""
     from .backend import get_backend
     from .fields import ScalarField
