@@ -719,7 +719,7 @@ int pdehip_jit_fixedpoint_run(const pdehip_grid_t *g, const pdehip_jit_pass_t *p
  * w = -A r that also leaves every wave's share of r.r and r.w (poisson_apply_kernel behind the ghost kernel; fp64 partial sums in fixed
  * slots, no atomics), a one-workgroup kernel (sums in a fixed order, alpha, beta, stop test `||r|| <= max(rtol * ||f - v||, atol)`, control
  * block) and one pointwise sweep (p, q, x, r).  The host enqueues `batch` iterations, whose launches return at entry once the solve
- * is over, and reads the 128-byte control block through pinned memory once per batch; results do not depend on the batch size and
+ * is over, and reads the control block through pinned memory once per batch; results do not depend on the batch size and
  * two runs give equal bits.  Fields fp64 or fp32; work vectors and scalars are fp64 either way.
  *
  * Faces: first-order conditions whose virtual point comes from the adjacent cell (Dirichlet, Neumann, mixed / Robin; scalar or
@@ -732,7 +732,8 @@ int pdehip_jit_fixedpoint_run(const pdehip_grid_t *g, const pdehip_jit_pass_t *p
  * (common.py:112-141).  Here the mean of the right-hand side is projected out, the iterates start from 0, the mean of x is removed
  * at the end, and one more sweep counts the cells with |A x - (f - v)| > 1e-5 + 1e-5 |f - v|: status 4 if there are any.
  *
- * The handle owns the five work vectors (x, r, p, q, w), the slots, the control block and its pinned mirror; it serves any number of
+ * The handle owns the five work vectors (x, r, p, q, w), the control block with its slots (three partial sums for each of the 32768
+ * waves a launch of the solver has at most: 786 KB whatever the grid) and its pinned mirror; it serves any number of
  * right-hand sides.  `rhs_full` and `out_full` are full arrays of the grid (only interior cells are read / written; they may be the
  * same array). */
 typedef struct pdehip_poisson {
@@ -757,8 +758,8 @@ int pdehip_poisson_destroy(void *handle);
  * longer depends on it.  pdehip_poisson_set_multigrid builds the hierarchy on a handle (`opts` = NULL drops it); pdehip_poisson_solve
  * on a handle with a hierarchy runs the PRECONDITIONED single-reduction loop: z = M r, w = -A z with the shares of r.z, z.w and r.r
  * in the sweep, beta = r.z / (r.z)_prev, alpha = r.z / (z.w - beta r.z / alpha_prev), p = z + beta p, q = w + beta q, x += alpha p,
- * r -= alpha q.  The stop rule is the one of the plain loop, on the true residual norm sqrt(r.r): `rtol` means the same thing for
- * both.  Status, singular systems, batches and bit-reproducibility as above.
+ * r -= alpha q.  The one-workgroup kernel and the pointwise sweep are those of the plain loop (which is the case z = r); the stop rule
+ * is the same, on the true residual norm sqrt(r.r): `rtol` means the same thing for both.  Status, singular systems, batches and bit-reproducibility as above.
  *
  * The cycle: level l+1 halves every axis of level l whose extent is even and >= 4 (the other axes keep extent and spacing) until no
  * axis qualifies, a level has <= 512 cells, or `max_levels` levels exist.  Every level carries the rediscretised Laplacian with the
@@ -769,7 +770,7 @@ int pdehip_poisson_destroy(void *handle);
  * LIMIT: an odd extent stops the coarsening of its axis (513^3 has one level, 500 x 500 x 300 ends at 125 x 125 x 75); the cycle is
  * then a weaker preconditioner and the sweeps of a large last level run one launch each - correct, but slower.
  * MEMORY: level 0 adds one work vector to the five of the handle, every further level three vectors of its size - in 3-D about
- * 3/7 of a work vector in all - and three partial sums per wave. */
+ * 3/7 of a work vector in all (`bytes`; the partial sums of the loop are in the slots of the handle and not counted). */
 #define PDEHIP_MG_MAX_LEVELS 32
 typedef struct pdehip_poisson_mg {
     int32_t smooth;              /* in: Jacobi sweeps before and after the coarse-grid correction; 0: 2.  out: the value used */

@@ -82,44 +82,72 @@ __device__ __forceinline__ long xcd_swizzle(long bid, long nblocks)
     return (bid % 8) * per + bid / 8;
 }
 
-// ---- fixed-point solvers (implicit Euler, Crank-Nicolson): control block and the deterministic convergence norm ----------
-// One device allocation: this block, then (at kFixedPointSlots doubles from its start) one partial sum per wave of the sweep that
-// ran last.  The stage sweeps get its address as LapArgs::st_err (st_kind 5).  Kernels only READ `stop`, at entry; the final sum
-// (fixedpoint_finish_kernel) is the only writer after the start of a step.  Nothing on the device waits for it.
-struct FixedPointCtl {
-    double err;          // mean |new - prev|^2 of the iteration that ran last
-    long long evals;     // right-hand-side evaluations counted on the device (one per iteration)
-    int iters;           // iterations done in this step
-    int converged;       // the stop test err < maxerr2 held
-    int failed;          // maxiter iterations without convergence
-    int stop;            // converged | failed: every later launch of the step returns at once
-    int nslots;          // partial sums the last sweep wrote (waves of its launch)
+// ---- device-side loops (fixed-point solvers, Poisson solver): control-block head and the deterministic wave partials ------------
+// The words every sweep of such a loop touches: first member of FixedPointCtl (below) and PoissonCtl (pdehip_poisson.h).  Sweeps only
+// READ `stop`, at entry, and announce their slot count; the one-workgroup kernel behind a sweep (final sums in a fixed order, stop
+// test) is the only writer of the rest after the start of a step / solve.  Nothing on the device waits for it.
+struct CtlHead {
+    int stop;            // converged | failed: every later launch of the step / solve returns at once
+    int nslots;          // waves of the sweep that ran last (each left its partial sums in its slot)
+    int capacity;        // waves the slots behind the block hold
+    int iters;           // iterations done in this step / solve
+    int converged;       // the stop test held
+    int failed;          // 1: maxiter iterations without convergence; other values: see the block that contains the head
     int maxiter;
-    double maxerr2;
-    double size;         // values the mean is taken over (complex pairs count once)
-    int capacity;        // slots behind the block
     int reserved;
 };
-constexpr int kFixedPointSlots = 8;   // doubles in front of the partial sums (sizeof(FixedPointCtl) <= 64)
-static_assert(sizeof(FixedPointCtl) <= kFixedPointSlots * sizeof(double), "the control block overlaps its partial sums");
-
-// entry of a fixed-point sweep: one uniform scalar load
-__device__ __forceinline__ bool fixedpoint_stopped(const double *ctl) { return ((const FixedPointCtl *)ctl)->stop != 0; }
-// ... and, when the sweep runs, the number of partial sums it will leave (waves of the launch; written by its first thread)
-__device__ __forceinline__ void fixedpoint_announce(double *ctl, long nslots)
+// entry of a sweep: one uniform scalar load
+__device__ __forceinline__ bool ctl_stopped(const CtlHead &h) { return h.stop != 0; }
+// ... and, when the sweep runs, the number of slots it will fill (waves of the launch; written by its first thread)
+__device__ __forceinline__ void ctl_announce(CtlHead &h, long nslots)
 {
-    if (blockIdx.x == 0 && threadIdx.x == 0) ((FixedPointCtl *)ctl)->nslots = (int)nslots;
+    if (blockIdx.x == 0 && threadIdx.x == 0) h.nslots = (int)nslots;
 }
-// end of a fixed-point sweep: butterfly sum over the wave (both partners add the same two numbers: every lane ends with the same
-// bits, in an order fixed by the lane numbers), one store per wave to its slot.  No atomics.
-// `slot`: the wave's number in the launch - fixed by the launch geometry alone.  (The stencil sweeps are short of SCALAR registers - some
-// instances sit at 100 of 102 -: they compute the slot from threadIdx at entry, which keeps it in a vector register, announce the slot count
-// there too, where `nblocks` is live anyway, and never read blockDim / gridDim, which would cost the pointer to the dispatch packet.)
-__device__ __forceinline__ void fixedpoint_wave_partial(double *ctl, double esum, int slot)
+// end of a sweep: butterfly sum over the wave (both partners add the same two numbers: every lane ends with the same bits, in an
+// order fixed by the lane numbers) ...
+__device__ __forceinline__ double wave_sum(double v)
 {
 #pragma unroll
-    for (int ofs = 32; ofs >= 1; ofs >>= 1) esum = esum + __shfl_xor(esum, ofs, 64);
-    if ((threadIdx.x & 63) == 0 && slot < ((const FixedPointCtl *)ctl)->capacity) ctl[kFixedPointSlots + slot] = esum;   // (the buffer holds any launch: pdehip_fixedpoint_ctl_bytes)
+    for (int ofs = 32; ofs >= 1; ofs >>= 1) v = v + __shfl_xor(v, ofs, 64);
+    return v;
+}
+// ... of each of N columns; lane 0 stores the N sums interleaved at slots[N * slot + q].  No atomics.  `slot`: the wave's number in the
+// launch - fixed by the launch geometry alone.  `capacity` is a reference so that only the storing lane loads it.  (sum_slots,
+// pdehip_sweep.h, is the other half.)
+template <int N>
+__device__ __forceinline__ void wave_partials(double *slots, const double (&s)[N], int slot, const int &capacity)
+{
+    double v[N];
+#pragma unroll
+    for (int q = 0; q < N; q++) v[q] = wave_sum(s[q]);
+    if ((threadIdx.x & 63) == 0 && slot < capacity)
+#pragma unroll
+        for (int q = 0; q < N; q++) slots[N * slot + q] = v[q];
+}
+
+// ---- fixed-point solvers (implicit Euler, Crank-Nicolson): control block and the convergence norm ------------------------------
+// One device allocation: this block, then (at kFixedPointSlots doubles from its start) one partial sum per wave of the sweep that
+// ran last (any launch fits: pdehip_fixedpoint_ctl_bytes).  The stage sweeps get its address as LapArgs::st_err (st_kind 5).
+struct FixedPointCtl {
+    CtlHead head;        // failed = 2: the partial sums did not fit (internal)
+    double err;          // mean |new - prev|^2 of the iteration that ran last
+    long long evals;     // right-hand-side evaluations counted on the device (one per iteration)
+    double maxerr2;
+    double size;         // values the mean is taken over (complex pairs count once)
+};
+constexpr int kFixedPointSlots = 8;   // doubles in front of the partial sums
+static_assert(sizeof(FixedPointCtl) <= kFixedPointSlots * sizeof(double), "the control block overlaps its partial sums");
+
+// The stage sweeps (pdehip_march.inc) know the block as LapArgs::st_err.  (They are short of SCALAR registers - some instances sit at
+// 100 of 102 -: they compute the slot from threadIdx at entry, which keeps it in a vector register, announce the slot count there too,
+// where `nblocks` is live anyway, and never read blockDim / gridDim, which would cost the pointer to the dispatch packet.  Their register
+// allocation also moves with the shape of this code: the one-column tail is spelled out instead of going through wave_partials<1>.)
+__device__ __forceinline__ bool fixedpoint_stopped(const double *ctl) { return ctl_stopped(((const FixedPointCtl *)ctl)->head); }
+__device__ __forceinline__ void fixedpoint_announce(double *ctl, long nslots) { ctl_announce(((FixedPointCtl *)ctl)->head, nslots); }
+__device__ __forceinline__ void fixedpoint_wave_partial(double *ctl, double esum, int slot)
+{
+    esum = wave_sum(esum);
+    if ((threadIdx.x & 63) == 0 && slot < ((const FixedPointCtl *)ctl)->head.capacity) ctl[kFixedPointSlots + slot] = esum;
 }
 
 template <int MODE>

@@ -5,7 +5,8 @@
 // until mean |x_new - x|^2 < maxerror^2.  Every iteration is ONE sweep where the stage kernels carry the epilogue (StageFuse kind 5:
 // update and the wave's share of the norm), else the slope into a scratch array and the pointwise fixedpoint_combine_kernel.  A
 // one-workgroup kernel behind it sums the shares in a fixed order, does the stop test ON THE DEVICE and writes the control block
-// (FixedPointCtl, pdehip_device.h).
+// (FixedPointCtl, pdehip_device.h; the two halves of the sum, wave_sum and sum_slots of pdehip_sweep.h, and the head of the block
+// are those of every device-side loop).
 //
 // The host does not synchronise per iteration: it enqueues a BATCH of iterations - every launch of a batch reads the block's `stop`
 // word at entry and returns at once when the step is over - and reads the block back through pinned memory once per batch.  A
@@ -87,21 +88,21 @@ int run(Eval &ev, const pdehip_grid_t *g, int ncomp, double size, pdehip_fixedpo
                 SLAB_TRY(fixedpoint_finish(ctl_dev, st));
             }
             SLAB_TRY(fixedpoint_read(&host, ctl_dev, st));
-            if (host.stop) break;
-            if (enq >= p->maxiter || host.iters != enq) return fixedpoint_fail(3, "internal: the fixed-point control block is out of step with the host");
+            if (host.head.stop) break;
+            if (enq >= p->maxiter || host.head.iters != enq) return fixedpoint_fail(3, "internal: the fixed-point control block is out of step with the host");
         }
-        p->evaluations += host.iters;
+        p->evaluations += host.head.iters;
         p->err = host.err;
-        p->last_iterations = host.iters;
-        if (p->iterations) p->iterations[s] = host.iters;
-        if (host.failed) {
-            if (host.failed != 1) return fixedpoint_fail(3, "internal: the partial sums of the fixed-point norm do not fit their buffer");
+        p->last_iterations = host.head.iters;
+        if (p->iterations) p->iterations[s] = host.head.iters;
+        if (host.head.failed) {
+            if (host.head.failed != 1) return fixedpoint_fail(3, "internal: the partial sums of the fixed-point norm do not fit their buffer");
             p->status = 1;   // maxiter iterations without convergence: the remaining steps are not enqueued
             *result = cur;
             return 0;
         }
         // iteration n wrote fb for odd n, fa for even n; the two other buffers are free again
-        void *res = (host.iters % 2 == 1) ? fb : fa, *other = (host.iters % 2 == 1) ? fa : fb;
+        void *res = (host.head.iters % 2 == 1) ? fb : fa, *other = (host.head.iters % 2 == 1) ? fa : fb;
         fa = other; fb = cur; cur = res;
         p->steps_done++;
     }

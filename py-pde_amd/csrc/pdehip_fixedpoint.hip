@@ -1,61 +1,49 @@
 // pdehip_fixedpoint.hip — what the fixed-point solvers (pdehip_fixedpoint.h) need besides the stage sweeps: the control block's kernels
 // (start of a call, start of a step, final sum + stop test), the pointwise form of the iteration for right-hand sides whose sweep
 // cannot carry it, and the read-back through pinned memory.
-#include "pdehip_common.h"
+#include "pdehip_sweep.h"
 #include "pdehip_fixedpoint.h"
 
 namespace pdehip {
 
 namespace {
 
-struct DevGridFp {
-    long n0, n1, n2;
-    long p0, p1, pc, off;
-};
-
 // start of a call: parameters of the stop test, counters of the call
 __global__ void fixedpoint_init_kernel(FixedPointCtl *c, int maxiter, double maxerr2, double size, int capacity)
 {
-    c->err = 0; c->evals = 0; c->iters = 0; c->converged = 0; c->failed = 0; c->stop = 0; c->nslots = 0;
-    c->maxiter = maxiter; c->maxerr2 = maxerr2; c->size = size; c->capacity = capacity;
+    c->head = CtlHead{0, 0, capacity, 0, 0, 0, maxiter, 0};
+    c->err = 0; c->evals = 0; c->maxerr2 = maxerr2; c->size = size;
 }
 
 // start of a step (after a failed step nothing runs any more: `stop` stays)
 __global__ void fixedpoint_begin_kernel(FixedPointCtl *c)
 {
-    if (c->failed) return;
-    c->iters = 0; c->converged = 0; c->stop = 0;
+    if (c->head.failed) return;
+    c->head.iters = 0; c->head.converged = 0; c->head.stop = 0;
 }
 
-// The final sum of an iteration and its stop test (implicit.py:99-104, crank_nicolson.py:105-110: `err / state.size < maxerror**2`).
-// ONE workgroup: thread i adds the slots i, i + 256, ... in that order, then a tree over the 256 sums in LDS - the same order in every run.
-__global__ void __launch_bounds__(256) fixedpoint_finish_kernel(double *ctl)
+// The final sum of an iteration (sum_slots: one workgroup, a fixed order) and its stop test (implicit.py:99-104,
+// crank_nicolson.py:105-110: `err / state.size < maxerror**2`).
+__global__ void __launch_bounds__(256) fixedpoint_finish_kernel(FixedPointCtl *c)
 {
-    FixedPointCtl *c = (FixedPointCtl *)ctl;
-    if (c->stop) return;   // uniform
-    __shared__ double part[256];
-    const int n = c->nslots < c->capacity ? c->nslots : c->capacity;
-    double s = 0;
-    for (int i = threadIdx.x; i < n; i += 256) s = s + ctl[kFixedPointSlots + i];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = 128; w >= 1; w >>= 1) {
-        if ((int)threadIdx.x < w) part[threadIdx.x] = part[threadIdx.x] + part[threadIdx.x + w];
-        __syncthreads();
-    }
+    CtlHead &h = c->head;
+    if (h.stop) return;   // uniform
+    double sum[1];
+    sum_slots<1>((const double *)c + kFixedPointSlots, ctl_nslots(h), sum);
     if (threadIdx.x == 0) {
-        const double err = part[0] / c->size;
+        const double err = sum[0] / c->size;
         c->err = err;
-        c->iters = c->iters + 1;
+        h.iters = h.iters + 1;
         c->evals = c->evals + 1;
-        if (c->nslots > c->capacity) { c->failed = 2; c->stop = 1; }   // (never: the buffer is sized for any launch geometry)
-        else if (err < c->maxerr2) { c->converged = 1; c->stop = 1; }   // false for NaN, like the reference
-        else if (c->iters >= c->maxiter) { c->failed = 1; c->stop = 1; }
+        if (h.nslots > h.capacity) { h.failed = 2; h.stop = 1; }   // (never: the buffer is sized for any launch geometry)
+        else if (err < c->maxerr2) { h.converged = 1; h.stop = 1; }   // false for NaN, like the reference
+        else if (h.iters >= h.maxiter) { h.failed = 1; h.stop = 1; }
     }
 }
 
 struct CombineArgs {
-    DevGridFp g;
+    RowGrid g;
+    long pc;   // elements between two components
     int ncomp;
     const void *prev, *k, *state_t, *rate_t;
     void *out;
@@ -79,7 +67,7 @@ __global__ void __launch_bounds__(256) fixedpoint_combine_kernel(CombineArgs a)
         const long j = r % a.g.n1; r /= a.g.n1;
         const long i = r % a.g.n0;
         const long comp = r / a.g.n0;
-        const long e = comp * a.g.pc + a.g.off + i * a.g.p0 + j * a.g.p1 + kk;
+        const long e = comp * a.pc + a.g.off + i * a.g.p0 + j * a.g.p1 + kk;
         const double pv = (double)((const T *)a.prev)[e], kn = (double)((const T *)a.k)[e], yv = (double)((const T *)a.state_t)[e];
         double nv;
         if (!a.rate_t) {
@@ -93,7 +81,7 @@ __global__ void __launch_bounds__(256) fixedpoint_combine_kernel(CombineArgs a)
         const double df = (double)o - pv;
         esum = esum + df * df;
     }
-    fixedpoint_wave_partial(a.ctl, esum, (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)));
+    fixedpoint_wave_partial(a.ctl, esum, wave_slot());
 }
 
 thread_local FixedPointCtl *g_pinned = nullptr;
@@ -121,7 +109,7 @@ int fixedpoint_begin(double *ctl_dev, void *st)
 
 int fixedpoint_finish(double *ctl_dev, void *st)
 {
-    hipLaunchKernelGGL(fixedpoint_finish_kernel, dim3(1), dim3(256), 0, as_stream(st), ctl_dev);
+    hipLaunchKernelGGL(fixedpoint_finish_kernel, dim3(1), dim3(256), 0, as_stream(st), (FixedPointCtl *)ctl_dev);
     PDEHIP_HIP(hipGetLastError());
     return 0;
 }
@@ -133,14 +121,12 @@ int fixedpoint_combine(const pdehip_grid_t *g, int ncomp, const void *prev, cons
     PDEHIP_TRY(norm_grid(g, &n));
     if (!prev || !k || !state_t || !out || !ctl_dev || ncomp < 1) PDEHIP_FAIL(E_VALUE, "fixedpoint_combine: NULL pointer");
     CombineArgs a;
-    a.g.n0 = n.n[0]; a.g.n1 = n.n[1]; a.g.n2 = n.n[2]; a.g.p0 = n.p[0]; a.g.p1 = n.p[1]; a.g.pc = n.pc; a.g.off = n.off;
+    a.g = make_row_grid(n); a.pc = n.pc;
     a.ncomp = ncomp; a.prev = prev; a.k = k; a.state_t = state_t; a.rate_t = rate_t; a.out = out; a.c = c; a.a_prev = a_prev; a.a_cn = a_cn; a.ctl = ctl_dev;
     const long items = (long)ncomp * n.n[0] * n.n[1] * n.n[2];
-    long blocks = (items + 1023) / 1024;   // four cells per thread
-    if (blocks < 1) blocks = 1;
-    if (blocks > 8192) blocks = 8192;
-    if (n.dtype == PDEHIP_F64) hipLaunchKernelGGL((fixedpoint_combine_kernel<double>), dim3((unsigned)blocks), dim3(256), 0, as_stream(st), a);
-    else hipLaunchKernelGGL((fixedpoint_combine_kernel<float>), dim3((unsigned)blocks), dim3(256), 0, as_stream(st), a);
+    const unsigned blocks = blocks_for((items + 3) / 4);   // four cells per thread
+    if (n.dtype == PDEHIP_F64) hipLaunchKernelGGL((fixedpoint_combine_kernel<double>), dim3(blocks), dim3(256), 0, as_stream(st), a);
+    else hipLaunchKernelGGL((fixedpoint_combine_kernel<float>), dim3(blocks), dim3(256), 0, as_stream(st), a);
     PDEHIP_HIP(hipGetLastError());
     return 0;
 }
@@ -148,10 +134,7 @@ int fixedpoint_combine(const pdehip_grid_t *g, int ncomp, const void *prev, cons
 int fixedpoint_read(FixedPointCtl *host, const double *ctl_dev, void *st)
 {
     if (!g_pinned) PDEHIP_HIP(hipHostMalloc((void **)&g_pinned, sizeof(FixedPointCtl), hipHostMallocDefault));
-    PDEHIP_HIP(hipMemcpyAsync(g_pinned, ctl_dev, sizeof(FixedPointCtl), hipMemcpyDeviceToHost, as_stream(st)));
-    PDEHIP_HIP(hipStreamSynchronize(as_stream(st)));
-    *host = *g_pinned;
-    return 0;
+    return read_ctl(host, g_pinned, ctl_dev, sizeof(FixedPointCtl), st);
 }
 
 void fixedpoint_note(bool fused, const char *sweep)
@@ -176,9 +159,9 @@ int pdehip_fixedpoint_ctl_bytes(const pdehip_grid_t *g, int ncomp, size_t *bytes
     PDEHIP_TRY(norm_grid(g, &n));
     if (!bytes || ncomp < 1) PDEHIP_FAIL(E_VALUE, "fixedpoint_ctl_bytes: NULL pointer");
     // one slot per wave of the sweep that writes them: a wave owns at least one piece of 64 cells of one row over one or more planes,
-    // a workgroup has at most 16 waves stacked along the rows (idle ones included); the pointwise form launches at most 8192 x 4 waves
+    // a workgroup has at most 16 waves stacked along the rows (idle ones included); the pointwise form launches at most kSweepWavesMax
     const size_t waves = (size_t)n.n[0] * (size_t)(n.n[1] + 16) * (size_t)(n.n[2] / 64 + 1);
-    const size_t slots = waves > 32768 ? waves : 32768;
+    const size_t slots = waves > (size_t)kSweepWavesMax ? waves : (size_t)kSweepWavesMax;
     *bytes = (kFixedPointSlots + slots) * sizeof(double);
     return 0;
 }

@@ -13,8 +13,10 @@
 // in the same pass, every wave's share of r.r and r.w; the ghost cells of r are set by the ghost kernel in front of it (faces only: a
 // launch over O(N^2) cells).  It is a kernel of its own: as one more run-time epilogue of lap_march_kernel the two sums cost instances
 // of the Runge-Kutta stage sweeps their last registers (scratch: 1072 bytes in the fp32 4 x 4 tile with tails, 68 in a contracted
-// fp64 one), and those sweeps are not to get slower for this.  A one-workgroup kernel adds the shares in a fixed order, derives alpha
-// and beta, does the stop test and writes the control block (PoissonCtl below).  Sweep 2 is pointwise: p = r + beta p, q = w + beta q, x += alpha p, r -= alpha q.  Every launch
+// fp64 one), and those sweeps are not to get slower for this.  A one-workgroup kernel (poisson_finish_kernel) adds the shares in a
+// fixed order, derives alpha and beta, does the stop test and writes the control block (PoissonCtl below).  Sweep 2
+// (poisson_update_kernel) is pointwise: p = r + beta p, q = w + beta q, x += alpha p, r -= alpha q.  Both are templates on PRECOND: the
+// preconditioned loop (pdehip_poisson_mg.h) is the same recurrence with z = M r in the place of r and its own sweep 1.  Every launch
 // reads the block's stop word at entry and returns at once when the solve is over; the host enqueues a batch of iterations and reads
 // the block through pinned memory once per batch.  Nothing on the device waits; the result does not depend on the batch size.
 //
@@ -23,26 +25,20 @@
 
 #include <cstddef>
 
-#include "pdehip_common.h"
+#include "pdehip_sweep.h"
 
 namespace pdehip {
 
-// Control block and the two deterministic dot products.  One device allocation like the fixed-point block (pdehip_device.h): this
-// block, then (at kPoissonSlots doubles from its start) TWO partial sums per wave of the sweep that ran last.  `stop`, `nslots` and
-// `capacity` sit where FixedPointCtl has them, so fixedpoint_stopped and fixedpoint_announce serve both.  Only the one-workgroup
-// kernels write the block during a solve.
+// Control block and the deterministic dot products.  One device allocation like the fixed-point block (pdehip_device.h): this block,
+// then (at kPoissonSlots doubles from its start) up to kPoissonColumns interleaved partial sums per wave of the sweep that ran last:
+// two in the plain loop (r.r, r.w) and around a solve, three in the preconditioned loop (r.z, z.w, r.r).  Every kernel of the solver is
+// launched through blocks_for, so kSweepWavesMax slots hold any launch.  Only the one-workgroup kernels write the block during a solve.
 struct PoissonCtl {
-    double rr;           // r.r of the iteration that ran last
-    double rw;           // r.w, w = -A r
-    int iters;           // updates of x done
-    int converged;       // ||r|| <= tol held
-    int failed;          // 1: maxiter updates without convergence, 2: a non-finite scalar, 3: breakdown (r.w <= 0 or p.q <= 0 for a definite system), 4: internal
-    int stop;            // converged | failed: every later launch of the solve returns at once
-    int nslots;          // waves of the last sweep (two partial sums each)
-    int maxiter;
+    CtlHead head;        // iters: updates of x done; failed = 2: a non-finite scalar, 3: breakdown (r.z, z.w or p.q <= 0 for a definite system), 4: internal
+    double rr;           // r.r of the iteration that ran last: the stop test is sqrt(rr) <= tol
+    double rw;           // delta = z.w, w = -A z (z = r in the plain loop)
+    double gamma;        // r.z (equal to rr in the plain loop)
     double alpha, beta;  // step lengths of the update that follows (Chronopoulos-Gear)
-    int capacity;        // waves the buffer behind the block holds
-    int reserved;
     double bnorm;        // ||b||_2, b = the right-hand side of the split system (r of iteration 0)
     double tol;          // max(rtol * ||b||, atol)
     double rtol, atol;
@@ -51,24 +47,11 @@ struct PoissonCtl {
     double count;        // singular systems: cells that violate |A x - b| <= 1e-5 + 1e-5 |b|
     double resid2;       // singular systems: |A x - b|^2 of that test
 };
-constexpr int kPoissonSlots = 16;   // doubles in front of the partial sums
-static_assert(sizeof(PoissonCtl) == kPoissonSlots * sizeof(double), "the control block of the Poisson solver overlaps its partial sums");
-static_assert(offsetof(PoissonCtl, stop) == offsetof(FixedPointCtl, stop) && offsetof(PoissonCtl, nslots) == offsetof(FixedPointCtl, nslots) &&
-              offsetof(PoissonCtl, capacity) == offsetof(FixedPointCtl, capacity), "fixedpoint_stopped / fixedpoint_announce read both control blocks");
-// end of a sweep of the solver: the butterfly sums of fixedpoint_wave_partial for both dot products (every lane ends with the same
-// bits, in an order fixed by the lane numbers), two stores per wave into its slots.  No atomics.
-__device__ __forceinline__ void poisson_wave_partial(double *ctl, double s_rr, double s_rw, int slot)
-{
-#pragma unroll
-    for (int ofs = 32; ofs >= 1; ofs >>= 1) {
-        s_rr = s_rr + __shfl_xor(s_rr, ofs, 64);
-        s_rw = s_rw + __shfl_xor(s_rw, ofs, 64);
-    }
-    if ((threadIdx.x & 63) == 0 && slot < ((const PoissonCtl *)ctl)->capacity) {
-        ctl[kPoissonSlots + 2 * slot] = s_rr;
-        ctl[kPoissonSlots + 2 * slot + 1] = s_rw;
-    }
-}
+constexpr int kPoissonSlots = 24;     // doubles in front of the partial sums
+constexpr int kPoissonColumns = 3;
+static_assert(sizeof(PoissonCtl) <= kPoissonSlots * sizeof(double), "the control block of the Poisson solver overlaps its partial sums");
+constexpr size_t kPoissonCtlBytes = (kPoissonSlots + (size_t)kPoissonColumns * kSweepWavesMax) * sizeof(double);
+__device__ __forceinline__ double *poisson_slots(PoissonCtl *c) { return (double *)c + kPoissonSlots; }
 
 struct PoissonMg;   // pdehip_poisson_mg.hip: the hierarchy of the multigrid preconditioner
 
@@ -81,8 +64,7 @@ struct PoissonHandle {
     double *zero_face = nullptr;   // the `const_arr` of the homogeneous copy of faces with coefficient arrays
     double *x = nullptr, *r = nullptr, *p = nullptr, *q = nullptr, *w = nullptr;
     size_t vec_bytes = 0;
-    double *ctl = nullptr;         // PoissonCtl + two partial sums per wave
-    int capacity = 0;
+    PoissonCtl *ctl = nullptr;     // the block and its slots: kPoissonCtlBytes
     PoissonCtl *pinned = nullptr;
     bool singular = false;         // every face periodic or Neumann: A has the constants in its null space
     PoissonMg *mg = nullptr;       // pdehip_poisson_set_multigrid: the solve runs the preconditioned loop (pdehip_poisson_mg.h)

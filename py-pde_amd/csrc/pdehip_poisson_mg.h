@@ -11,9 +11,10 @@
 // (P = 2^k R^T).  Same sweeps before and after, a symmetric smoother, P ~ R^T: M is symmetric and positive - a fixed linear operator,
 // so conjugate-gradient theory holds and results are reproducible.
 //
-// Loop (Chronopoulos-Gear, one reduction point per iteration): z = M r; w = -A z with every wave's share of r.z, z.w and r.r;
-// gamma = r.z, delta = z.w, beta = gamma / gamma_prev, alpha = gamma / (delta - beta gamma / alpha_prev); the stop test of the plain
-// loop on the TRUE residual norm sqrt(r.r); p = z + beta p, q = w + beta q, x += alpha p, r -= alpha q.
+// Loop (Chronopoulos-Gear, one reduction point per iteration): z = M r; w = -A z with every wave's share of r.z, z.w and r.r (sweep 1,
+// this file's poisson_mg_apply_kernel: three columns of the handle's slots).  Behind it the kernels of the plain loop with PRECOND
+// (pdehip_poisson.hip): gamma = r.z, delta = z.w, beta = gamma / gamma_prev, alpha = gamma / (delta - beta gamma / alpha_prev); the
+// stop test on the TRUE residual norm sqrt(r.r); p = z + beta p, q = w + beta q, x += alpha p, r -= alpha q.
 // Singular systems: A annihilates constants, so a constant component that M adds to z changes none of w, q, r, gamma (r has mean
 // zero: the right-hand side was projected) and delta; it only travels into x, whose mean is removed at the end as in the plain loop.
 #pragma once
@@ -24,9 +25,10 @@ namespace pdehip {
 
 int poisson_mg_set(PoissonHandle *h, pdehip_poisson_mg_t *opts);   // builds (opts != NULL) or drops the hierarchy of a handle
 void poisson_mg_release(PoissonHandle *h);
-// one iteration of the preconditioned loop behind the start of poisson_solve_t: cycle, sweep 1 with three sums, the one-workgroup
-// kernel, sweep 2.  Every launch returns at entry when the control block says the solve is over.
-int poisson_mg_iteration(PoissonHandle *h, void *st);
+// sweep 1 of the preconditioned loop: the cycle z = M r, then w = -A z with the three sums; *z = the array the cycle left z in.  The
+// one-workgroup kernel and sweep 2 behind it are those of the plain loop (pdehip_poisson.hip).  Every launch returns at entry when
+// the control block says the solve is over.
+int poisson_mg_sweep1(PoissonHandle *h, const double **z, void *st);
 void poisson_mg_note(const PoissonHandle *h);   // pdehip_last_kernel_name after a solve
 
 }  // namespace pdehip

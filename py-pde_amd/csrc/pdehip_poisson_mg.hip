@@ -1,4 +1,4 @@
-// pdehip_poisson_mg.hip — the multigrid V-cycle that preconditions the conjugate gradients of the Poisson solver, and the
+// pdehip_poisson_mg.hip — the multigrid V-cycle that preconditions the conjugate gradients of the Poisson solver, and sweep 1 of the
 // preconditioned loop (see pdehip_poisson_mg.h).  Kernels of a cycle on a level with `smooth` = 2:
 //   poisson_mg_smooth0_kernel   the first TWO Jacobi sweeps from a zero guess in one pass: z1 = omega r / d is pointwise in r, so
 //                               z2 = z1 + omega (r - (-A) z1) / d is a 7-point stencil on r with the diagonal taken from the position
@@ -16,9 +16,7 @@
 namespace pdehip {
 
 // what a kernel knows of a level
-struct MgDev {
-    long n0, n1, n2;       // cells (normalised axes; 1 on axes the grid does not have)
-    long p0, p1, off;      // pitches and the offset of cell (0, 0, 0)
+struct MgDev : RowGrid {
     int ndim;
     int loc[3];            // the axis has local faces (they enter the diagonal); 0: periodic or not there
     double s[3];           // 1 / dx^2; 0 on axes the grid does not have
@@ -38,14 +36,12 @@ struct MgLevel {
     long cells = 0;
 };
 
-constexpr int kMgHeader = 8;        // doubles in front of the partial sums of the preconditioned loop: [0] = gamma of the iteration before
 constexpr int kMgCoarseCells = 1024;   // the last level runs in LDS up to this many cells (4 per thread of one workgroup)
 
 struct PoissonMg {
     std::vector<MgLevel> lv;
     int smooth = 2, coarse_sweeps = 32;
     double omega = 0;
-    double *sums = nullptr;   // kMgHeader doubles, then THREE partial sums per wave of sweep 1 (the plain loop keeps its two-column slots)
     size_t bytes = 0;
 };
 
@@ -77,18 +73,11 @@ __device__ __forceinline__ long mg_above(long c, long n, int loc) { return c < n
 // The first sweep(s) from z = 0.  two == 0: z = omega r / d.  two != 0: the second sweep in the same pass.  z1 of a ghost cell is
 // omega r_ghost / d of the cell the ghost cell copies, because r_ghost = f r_adjacent (or the periodic image) is already in memory.
 template <int VEC>
-__global__ void __launch_bounds__(256) poisson_mg_smooth0_kernel(MgDev L, int two, const double *r, double *z, const double *ctl)
+__global__ void __launch_bounds__(256) poisson_mg_smooth0_kernel(MgDev L, int two, const double *r, double *z, const PoissonCtl *ctl)
 {
-    if (fixedpoint_stopped(ctl)) return;   // uniform
+    if (ctl_stopped(ctl->head)) return;   // uniform
     typedef double V __attribute__((ext_vector_type(VEC)));
-    const long per_row = L.n2 / VEC;
-    const long total = L.n0 * L.n1 * per_row;
-    for (long t = blockIdx.x * (long)blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
-        long rest = t;
-        const long k = (rest % per_row) * VEC; rest /= per_row;
-        const long j = rest % L.n1;
-        const long i = rest / L.n1;
-        const long e = L.off + i * L.p0 + j * L.p1 + k;
+    for_row_pieces<VEC>(L, [&](long i, long j, long k, long e) {
         const V c = *(const V *)(r + e);
         V wd, z1, out;
 #pragma unroll
@@ -98,7 +87,7 @@ __global__ void __launch_bounds__(256) poisson_mg_smooth0_kernel(MgDev L, int tw
         }
         if (!two) {
             *(V *)(z + e) = z1;
-            continue;
+            return;
         }
         const double left = mg_wd(L, i, j, mg_below(k, L.n2, L.loc[2])) * r[e - 1];
         const double right = mg_wd(L, i, j, mg_above(k + VEC - 1, L.n2, L.loc[2])) * r[e + VEC];
@@ -131,7 +120,7 @@ __global__ void __launch_bounds__(256) poisson_mg_smooth0_kernel(MgDev L, int tw
             out[m] = cen + wd[m] * (c[m] - az);
         }
         *(V *)(z + e) = out;
-    }
+    });
 }
 
 // (-A) z of VEC cells of a row; the ghost cells of z are in memory
@@ -156,41 +145,29 @@ __device__ __forceinline__ V mg_minus_a(const MgDev &L, const double *z, long e,
 
 // one Jacobi sweep: out = z + omega (r - (-A) z) / d
 template <int VEC>
-__global__ void __launch_bounds__(256) poisson_mg_sweep_kernel(MgDev L, const double *r, const double *z, double *out, const double *ctl)
+__global__ void __launch_bounds__(256) poisson_mg_sweep_kernel(MgDev L, const double *r, const double *z, double *out, const PoissonCtl *ctl)
 {
-    if (fixedpoint_stopped(ctl)) return;   // uniform
+    if (ctl_stopped(ctl->head)) return;   // uniform
     typedef double V __attribute__((ext_vector_type(VEC)));
-    const long per_row = L.n2 / VEC;
-    const long total = L.n0 * L.n1 * per_row;
-    for (long t = blockIdx.x * (long)blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
-        long rest = t;
-        const long k = (rest % per_row) * VEC; rest /= per_row;
-        const long j = rest % L.n1;
-        const long i = rest / L.n1;
-        const long e = L.off + i * L.p0 + j * L.p1 + k;
+    for_row_pieces<VEC>(L, [&](long i, long j, long k, long e) {
         const V c = *(const V *)(z + e), rv = *(const V *)(r + e);
         const V az = mg_minus_a<VEC, V>(L, z, e, c);
         V o;
 #pragma unroll
         for (int m = 0; m < VEC; m++) o[m] = c[m] + mg_wd(L, i, j, k + m) * (rv[m] - az[m]);
         *(V *)(out + e) = o;
-    }
+    });
 }
 
 // residual and restriction: rc(coarse cell) = mean over its children of r - (-A) z.  HZ = children along the fastest axis (2: one
 // 16-byte access per row of children); h0, h1 = children along the two other axes.  Sum in a fixed order.
 template <int HZ>
-__global__ void __launch_bounds__(256) poisson_mg_restrict_kernel(MgDev L, MgDev C, int h0, int h1, const double *r, const double *z, double *rc, const double *ctl)
+__global__ void __launch_bounds__(256) poisson_mg_restrict_kernel(MgDev L, MgDev C, int h0, int h1, const double *r, const double *z, double *rc, const PoissonCtl *ctl)
 {
-    if (fixedpoint_stopped(ctl)) return;   // uniform
+    if (ctl_stopped(ctl->head)) return;   // uniform
     typedef double V __attribute__((ext_vector_type(HZ)));
-    const long total = C.n0 * C.n1 * C.n2;
     const double scale = 1.0 / (double)(h0 * h1 * HZ);
-    for (long t = blockIdx.x * (long)blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
-        long rest = t;
-        const long kc = rest % C.n2; rest /= C.n2;
-        const long jc = rest % C.n1;
-        const long ic = rest / C.n1;
+    for_row_pieces<1>(C, [&](long ic, long jc, long kc, long ec) {
         double sum = 0;
         for (int a = 0; a < h0; a++)
             for (int b = 0; b < h1; b++) {
@@ -200,39 +177,32 @@ __global__ void __launch_bounds__(256) poisson_mg_restrict_kernel(MgDev L, MgDev
 #pragma unroll
                 for (int m = 0; m < HZ; m++) sum = sum + (rv[m] - az[m]);
             }
-        rc[C.off + ic * C.p0 + jc * C.p1 + kc] = sum * scale;
-    }
+        rc[ec] = sum * scale;
+    });
 }
 
 // prolongation and correction: z += zc(parent); sh = 1 on the halved axes
 template <int VEC>
-__global__ void __launch_bounds__(256) poisson_mg_prolong_kernel(MgDev L, MgDev C, int sh0, int sh1, int sh2, const double *zc, double *z, const double *ctl)
+__global__ void __launch_bounds__(256) poisson_mg_prolong_kernel(MgDev L, MgDev C, int sh0, int sh1, int sh2, const double *zc, double *z, const PoissonCtl *ctl)
 {
-    if (fixedpoint_stopped(ctl)) return;   // uniform
+    if (ctl_stopped(ctl->head)) return;   // uniform
     typedef double V __attribute__((ext_vector_type(VEC)));
-    const long per_row = L.n2 / VEC;
-    const long total = L.n0 * L.n1 * per_row;
-    for (long t = blockIdx.x * (long)blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
-        long rest = t;
-        const long k = (rest % per_row) * VEC; rest /= per_row;
-        const long j = rest % L.n1;
-        const long i = rest / L.n1;
-        const long e = L.off + i * L.p0 + j * L.p1 + k;
+    for_row_pieces<VEC>(L, [&](long i, long j, long k, long e) {
         const long ec = C.off + (i >> sh0) * C.p0 + (j >> sh1) * C.p1;
         V v = *(const V *)(z + e);
 #pragma unroll
         for (int m = 0; m < VEC; m++) v[m] = v[m] + zc[ec + ((k + m) >> sh2)];
         *(V *)(z + e) = v;
-    }
+    });
 }
 
 // The last level in ONE workgroup: `sweeps` Jacobi sweeps from zero with the iterate in LDS (compact: cells, then one slot that stays
 // zero).  A thread owns up to four cells and keeps their omega r / d, omega / d and the LDS slots of their six neighbours; a
 // neighbour beyond a local face is the zero slot (the face is in the diagonal), one beyond a periodic end the cell at the other end:
 // z' = z + (omega / d) (r - d z + sum s_a (z_lower + z_upper)) = omega r / d + (1 - omega) z + (omega / d) sum s_a (z_lower + z_upper).
-__global__ void __launch_bounds__(256) poisson_mg_coarse_kernel(MgDev L, int sweeps, const double *r, double *z, const double *ctl)
+__global__ void __launch_bounds__(256) poisson_mg_coarse_kernel(MgDev L, int sweeps, const double *r, double *z, const PoissonCtl *ctl)
 {
-    if (fixedpoint_stopped(ctl)) return;   // uniform
+    if (ctl_stopped(ctl->head)) return;   // uniform
     __shared__ double buf[2][kMgCoarseCells + 1];
     const int cells = (int)(L.n0 * L.n1 * L.n2);
     constexpr int CPT = kMgCoarseCells / 256;
@@ -305,22 +275,15 @@ __global__ void __launch_bounds__(256) poisson_mg_face_kernel(const double *fine
     }
 }
 
-// sweep 1 of the preconditioned loop: w = -A z and the wave's shares of r.z, z.w and r.r (three columns of slots behind kMgHeader)
+// sweep 1 of the preconditioned loop: w = -A z and the wave's shares of r.z, z.w and r.r
 template <int VEC>
-__global__ void __launch_bounds__(256) poisson_mg_apply_kernel(MgDev L, const double *z, const double *r, double *w, double *ctl, double *sums)
+__global__ void __launch_bounds__(256) poisson_mg_apply_kernel(MgDev L, const double *z, const double *r, double *w, PoissonCtl *ctl)
 {
-    if (fixedpoint_stopped(ctl)) return;   // uniform
-    fixedpoint_announce(ctl, (long)gridDim.x * (blockDim.x >> 6));
+    if (ctl_stopped(ctl->head)) return;   // uniform
+    ctl_announce(ctl->head, (long)gridDim.x * (blockDim.x >> 6));
     typedef double V __attribute__((ext_vector_type(VEC)));
-    const long per_row = L.n2 / VEC;
-    const long total = L.n0 * L.n1 * per_row;
     double s_rz = 0, s_zw = 0, s_rr = 0;
-    for (long t = blockIdx.x * (long)blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
-        long rest = t;
-        const long k = (rest % per_row) * VEC; rest /= per_row;
-        const long j = rest % L.n1;
-        const long i = rest / L.n1;
-        const long e = L.off + i * L.p0 + j * L.p1 + k;
+    for_row_pieces<VEC>(L, [&](long, long, long, long e) {
         const V c = *(const V *)(z + e), rv = *(const V *)(r + e);
         const V az = mg_minus_a<VEC, V>(L, z, e, c);
 #pragma unroll
@@ -330,117 +293,12 @@ __global__ void __launch_bounds__(256) poisson_mg_apply_kernel(MgDev L, const do
             s_rr = s_rr + rv[m] * rv[m];
         }
         *(V *)(w + e) = az;
-    }
-#pragma unroll
-    for (int ofs = 32; ofs >= 1; ofs >>= 1) {
-        s_rz = s_rz + __shfl_xor(s_rz, ofs, 64);
-        s_zw = s_zw + __shfl_xor(s_zw, ofs, 64);
-        s_rr = s_rr + __shfl_xor(s_rr, ofs, 64);
-    }
-    const int slot = (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
-    if ((threadIdx.x & 63) == 0 && slot < ((const PoissonCtl *)ctl)->capacity) {
-        sums[kMgHeader + 3 * slot] = s_rz;
-        sums[kMgHeader + 3 * slot + 1] = s_zw;
-        sums[kMgHeader + 3 * slot + 2] = s_rr;
-    }
-}
-
-// Behind sweep 1: the three sums in a fixed order (thread i adds the slots i, i + 256, ..., then a tree in LDS), the stop test of
-// the plain loop on sqrt(r.r), and the step lengths of the update that follows.
-__global__ void __launch_bounds__(256) poisson_mg_finish_kernel(double *ctl, double *sums)
-{
-    PoissonCtl *c = (PoissonCtl *)ctl;
-    if (c->stop) return;   // uniform
-    __shared__ double part[3][256];
-    const int n = c->nslots < c->capacity ? c->nslots : c->capacity;
-    double s[3] = {0, 0, 0};
-    for (int i = threadIdx.x; i < n; i += 256)
-#pragma unroll
-        for (int q = 0; q < 3; q++) s[q] = s[q] + sums[kMgHeader + 3 * i + q];
-#pragma unroll
-    for (int q = 0; q < 3; q++) part[q][threadIdx.x] = s[q];
-    __syncthreads();
-    for (int w = 128; w >= 1; w >>= 1) {
-        if ((int)threadIdx.x < w)
-#pragma unroll
-            for (int q = 0; q < 3; q++) part[q][threadIdx.x] = part[q][threadIdx.x] + part[q][threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x != 0) return;
-    const double gamma = part[0][0], delta = part[1][0], rr = part[2][0];
-    const double gamma_prev = sums[0], alpha_prev = c->alpha;
-    sums[0] = gamma;
-    c->rr = rr;
-    c->rw = delta;
-    if (c->nslots > c->capacity) { c->failed = 4; c->stop = 1; return; }
-    if (c->iters == 0) {
-        c->bnorm = sqrt(rr);
-        const double t = c->rtol * c->bnorm;
-        c->tol = t > c->atol ? t : c->atol;
-    }
-    if (!isfinite(gamma) || !isfinite(delta) || !isfinite(rr)) { c->failed = 2; c->stop = 1; return; }
-    if (sqrt(rr) <= c->tol) { c->converged = 1; c->stop = 1; return; }
-    if (c->iters >= c->maxiter) { c->failed = 1; c->stop = 1; return; }
-    double beta = 0, denom = delta;
-    if (c->iters > 0) {
-        beta = gamma / gamma_prev;
-        denom = delta - beta * gamma / alpha_prev;
-    }
-    if (!(delta > 0) || !(denom > 0) || !(gamma > 0)) { c->failed = 3; c->stop = 1; return; }
-    c->alpha = gamma / denom;
-    c->beta = beta;
-    c->iters = c->iters + 1;
-}
-
-// sweep 2 of the preconditioned loop: p = z + beta p, q = w + beta q, x += alpha p, r -= alpha q
-template <int VEC>
-__global__ void __launch_bounds__(256) poisson_mg_update_kernel(MgDev L, double *x, double *r, double *p, double *q, const double *z, const double *w, const double *ctl)
-{
-    const PoissonCtl *c = (const PoissonCtl *)ctl;
-    if (c->stop) return;   // uniform
-    const double alpha = c->alpha, beta = c->beta;
-    typedef double V __attribute__((ext_vector_type(VEC)));
-    const long per_row = L.n2 / VEC;
-    const long total = L.n0 * L.n1 * per_row;
-    for (long t = blockIdx.x * (long)blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
-        long rest = t;
-        const long k = (rest % per_row) * VEC; rest /= per_row;
-        const long j = rest % L.n1;
-        const long i = rest / L.n1;
-        const long e = L.off + i * L.p0 + j * L.p1 + k;
-        const V zv = *(const V *)(z + e), wv = *(const V *)(w + e);
-        V pv = *(const V *)(p + e), qv = *(const V *)(q + e), xv = *(const V *)(x + e), rv = *(const V *)(r + e);
-#pragma unroll
-        for (int m = 0; m < VEC; m++) {
-            pv[m] = zv[m] + beta * pv[m];
-            qv[m] = wv[m] + beta * qv[m];
-            xv[m] = xv[m] + alpha * pv[m];
-            rv[m] = rv[m] - alpha * qv[m];
-        }
-        *(V *)(p + e) = pv;
-        *(V *)(q + e) = qv;
-        *(V *)(x + e) = xv;
-        *(V *)(r + e) = rv;
-    }
+    });
+    wave_partials<3>(poisson_slots(ctl), {s_rz, s_zw, s_rr}, wave_slot(), ctl->head.capacity);
 }
 
 // the stop word of a solve that is over would switch a lone application of the cycle off
-__global__ void poisson_mg_open_kernel(PoissonCtl *c) { c->stop = 0; }
-
-unsigned mg_blocks(long items)
-{
-    long b = (items + 255) / 256;
-    if (b < 1) b = 1;
-    if (b > 8192) b = 8192;   // at most 32768 waves: what the slots always hold
-    return (unsigned)b;
-}
-
-#define MG_LAUNCH(kernel, vec_even, items, st, ...)                                                                          \
-    do {                                                                                                                     \
-        if (vec_even) hipLaunchKernelGGL((kernel<2>), dim3(mg_blocks((items) / 2)), dim3(256), 0, as_stream(st), __VA_ARGS__); \
-        else hipLaunchKernelGGL((kernel<1>), dim3(mg_blocks(items)), dim3(256), 0, as_stream(st), __VA_ARGS__);              \
-        PDEHIP_HIP(hipGetLastError());                                                                                       \
-    } while (0)
+__global__ void poisson_mg_open_kernel(PoissonCtl *c) { c->head.stop = 0; }
 
 int mg_ghosts(const MgLevel &L, double *v, void *st) { return launch_ghosts(L.n, 1, L.faces, v, as_stream(st)); }
 
@@ -450,10 +308,10 @@ int mg_from_zero(PoissonHandle *h, MgLevel &L, int count, void *st)
     const bool even = L.n.n[2] % 2 == 0;
     const int two = count >= 2 ? 1 : 0;
     if (two) PDEHIP_TRY(mg_ghosts(L, L.r, st));
-    MG_LAUNCH(poisson_mg_smooth0_kernel, even, L.cells, st, L.dev, two, L.r, L.z, h->ctl);
+    PDEHIP_LAUNCH_ROWS(even, L.cells, st, poisson_mg_smooth0_kernel<VEC>, L.dev, two, L.r, L.z, h->ctl);
     for (int s = two ? 2 : 1; s < count; s++) {
         PDEHIP_TRY(mg_ghosts(L, L.z, st));
-        MG_LAUNCH(poisson_mg_sweep_kernel, even, L.cells, st, L.dev, L.r, L.z, L.t, h->ctl);
+        PDEHIP_LAUNCH_ROWS(even, L.cells, st, poisson_mg_sweep_kernel<VEC>, L.dev, L.r, L.z, L.t, h->ctl);
         double *sw = L.z; L.z = L.t; L.t = sw;
     }
     return 0;
@@ -476,14 +334,14 @@ int mg_cycle(PoissonHandle *h, size_t l, void *st)
     PDEHIP_TRY(mg_from_zero(h, L, mg->smooth, st));
     PDEHIP_TRY(mg_ghosts(L, L.z, st));
     const int h0 = L.half[0] ? 2 : 1, h1 = L.half[1] ? 2 : 1;
-    if (L.half[2]) hipLaunchKernelGGL((poisson_mg_restrict_kernel<2>), dim3(mg_blocks(C.cells)), dim3(256), 0, as_stream(st), L.dev, C.dev, h0, h1, L.r, L.z, C.r, h->ctl);
-    else hipLaunchKernelGGL((poisson_mg_restrict_kernel<1>), dim3(mg_blocks(C.cells)), dim3(256), 0, as_stream(st), L.dev, C.dev, h0, h1, L.r, L.z, C.r, h->ctl);
+    if (L.half[2]) hipLaunchKernelGGL((poisson_mg_restrict_kernel<2>), dim3(blocks_for(C.cells)), dim3(256), 0, as_stream(st), L.dev, C.dev, h0, h1, L.r, L.z, C.r, h->ctl);
+    else hipLaunchKernelGGL((poisson_mg_restrict_kernel<1>), dim3(blocks_for(C.cells)), dim3(256), 0, as_stream(st), L.dev, C.dev, h0, h1, L.r, L.z, C.r, h->ctl);
     PDEHIP_HIP(hipGetLastError());
     PDEHIP_TRY(mg_cycle(h, l + 1, st));
-    MG_LAUNCH(poisson_mg_prolong_kernel, even, L.cells, st, L.dev, C.dev, L.half[0], L.half[1], L.half[2], C.z, L.z, h->ctl);
+    PDEHIP_LAUNCH_ROWS(even, L.cells, st, poisson_mg_prolong_kernel<VEC>, L.dev, C.dev, L.half[0], L.half[1], L.half[2], C.z, L.z, h->ctl);
     for (int s = 0; s < mg->smooth; s++) {
         PDEHIP_TRY(mg_ghosts(L, L.z, st));
-        MG_LAUNCH(poisson_mg_sweep_kernel, even, L.cells, st, L.dev, L.r, L.z, L.t, h->ctl);
+        PDEHIP_LAUNCH_ROWS(even, L.cells, st, poisson_mg_sweep_kernel<VEC>, L.dev, L.r, L.z, L.t, h->ctl);
         double *sw = L.z; L.z = L.t; L.t = sw;
     }
     return 0;
@@ -506,8 +364,7 @@ void fill_dev(MgLevel &L, double omega)
     MgDev &d = L.dev;
     const NGrid &n = L.n;
     memset(&d, 0, sizeof(d));
-    d.n0 = n.n[0]; d.n1 = n.n[1]; d.n2 = n.n[2];
-    d.p0 = n.p[0]; d.p1 = n.p[1]; d.off = n.off;
+    static_cast<RowGrid &>(d) = make_row_grid(n);
     d.ndim = n.ndim;
     d.omega = omega;
     double d0 = 0;
@@ -543,7 +400,6 @@ void poisson_mg_release(PoissonHandle *h)
         for (double *a : L.arr)
             if (a) (void)hipFree(a);
     }
-    if (mg->sums) (void)hipFree(mg->sums);
     delete mg;
     h->mg = nullptr;
 }
@@ -611,7 +467,7 @@ int poisson_mg_set(PoissonHandle *h, pdehip_poisson_mg_t *o)
                     const long m1c = C.n.n[o1], m2c = C.n.n[o2];
                     alloc(&C.arr[q], (size_t)(m1c * m2c));
                     if (e != hipSuccess) break;
-                    hipLaunchKernelGGL(poisson_mg_face_kernel, dim3(mg_blocks(m1c * m2c)), dim3(256), 0, 0, ff.factor1_arr, C.arr[q], m1c, m2c, F.half[o1] ? 2 : 1, F.half[o2] ? 2 : 1, F.n.n[o2]);
+                    hipLaunchKernelGGL(poisson_mg_face_kernel, dim3(blocks_for(m1c * m2c)), dim3(256), 0, 0, ff.factor1_arr, C.arr[q], m1c, m2c, F.half[o1] ? 2 : 1, F.half[o2] ? 2 : 1, F.n.n[o2]);
                     if (e == hipSuccess) e = hipGetLastError();
                     cf.factor1_arr = C.arr[q];
                 }
@@ -626,7 +482,6 @@ int poisson_mg_set(PoissonHandle *h, pdehip_poisson_mg_t *o)
         if (e != hipSuccess) break;
     }
     alloc(&mg->lv[0].z, (size_t)(n0.pc + kAllocSlack));
-    alloc(&mg->sums, (size_t)kMgHeader + 3 * (size_t)h->capacity);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) {
         poisson_mg_release(h);
@@ -644,16 +499,13 @@ int poisson_mg_set(PoissonHandle *h, pdehip_poisson_mg_t *o)
     return 0;
 }
 
-int poisson_mg_iteration(PoissonHandle *h, void *st)
+int poisson_mg_sweep1(PoissonHandle *h, const double **z, void *st)
 {
-    PoissonMg *mg = h->mg;
     PDEHIP_TRY(mg_precondition(h, st));
-    MgLevel &L = mg->lv[0];
-    const bool even = L.n.n[2] % 2 == 0;
+    MgLevel &L = h->mg->lv[0];
     PDEHIP_TRY(mg_ghosts(L, L.z, st));
-    MG_LAUNCH(poisson_mg_apply_kernel, even, L.cells, st, L.dev, L.z, h->r, h->w, h->ctl, mg->sums);
-    hipLaunchKernelGGL(poisson_mg_finish_kernel, dim3(1), dim3(256), 0, as_stream(st), h->ctl, mg->sums);
-    MG_LAUNCH(poisson_mg_update_kernel, even, L.cells, st, L.dev, h->x, h->r, h->p, h->q, L.z, h->w, h->ctl);
+    PDEHIP_LAUNCH_ROWS(L.n.n[2] % 2 == 0, L.cells, st, poisson_mg_apply_kernel<VEC>, L.dev, L.z, h->r, h->w, h->ctl);
+    *z = L.z;
     return 0;
 }
 
@@ -684,7 +536,7 @@ int pdehip_poisson_precondition(void *handle, const void *r_full, void *z_full, 
     hipStream_t s = as_stream(stream);
     const size_t bytes = (size_t)h->n64.pc * sizeof(double);
     PDEHIP_HIP(hipMemcpyAsync(h->r, r_full, bytes, hipMemcpyDeviceToDevice, s));
-    hipLaunchKernelGGL(poisson_mg_open_kernel, dim3(1), dim3(1), 0, s, (PoissonCtl *)h->ctl);
+    hipLaunchKernelGGL(poisson_mg_open_kernel, dim3(1), dim3(1), 0, s, h->ctl);
     PDEHIP_HIP(hipGetLastError());
     PDEHIP_TRY(mg_precondition(h, stream));
     PDEHIP_HIP(hipMemcpyAsync(z_full, h->mg->lv[0].z, bytes, hipMemcpyDeviceToDevice, s));

@@ -1,0 +1,85 @@
+// pdehip_sweep.h — what the pointwise sweeps of the device-side loops (pdehip_fixedpoint.hip, pdehip_poisson.hip, pdehip_poisson_mg.hip)
+// share in the offline build: the row loop, the launch geometry, the final sum of the wave partials (wave_partials, pdehip_device.h, is
+// the other half) and the read-back of a control block.
+#pragma once
+
+#include "pdehip_common.h"
+
+namespace pdehip {
+
+// interior cell (i, j, k) of an array in the ghost-padded layout of norm_grid: element off + i * p0 + j * p1 + k
+struct RowGrid {
+    long n0, n1, n2;       // cells (normalised axes; 1 on axes the grid does not have)
+    long p0, p1, off;      // pitches and the offset of cell (0, 0, 0)
+};
+inline RowGrid make_row_grid(const NGrid &n) { return RowGrid{n.n[0], n.n[1], n.n[2], n.p[0], n.p[1], n.off}; }
+
+// A thread takes VEC cells of a row (16-byte accesses where the row length is even), pieces in a grid-stride loop: a fixed order per
+// thread.  fn(i, j, k, element of the first cell of the piece).
+template <int VEC, class F>
+__device__ __forceinline__ void for_row_pieces(const RowGrid &g, F &&fn)
+{
+    const long per_row = g.n2 / VEC;
+    const long total = g.n0 * g.n1 * per_row;
+    for (long t = blockIdx.x * (long)blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
+        long rest = t;
+        const long k = (rest % per_row) * VEC; rest /= per_row;
+        const long j = rest % g.n1;
+        const long i = rest / g.n1;
+        fn(i, j, k, g.off + i * g.p0 + j * g.p1 + k);
+    }
+}
+__device__ __forceinline__ int wave_slot() { return (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)); }
+
+// workgroups of 256 threads for `items` pieces; the cap bounds the waves of a launch and with them the slots a loop needs
+constexpr long kSweepBlocksMax = 8192;
+constexpr int kSweepWavesMax = (int)(kSweepBlocksMax * (256 / 64));
+inline unsigned blocks_for(long items)
+{
+    const long b = (items + 255) / 256;
+    return (unsigned)(b < 1 ? 1 : (b > kSweepBlocksMax ? kSweepBlocksMax : b));
+}
+// launch of a row sweep over `cells` cells: `kernel` names its instance with VEC, which is 2 where the row length is even, else 1
+#define PDEHIP_LAUNCH_ROWS(even, cells, st, kernel, ...)                                                                              \
+    do {                                                                                                                             \
+        if (even) { constexpr int VEC = 2; hipLaunchKernelGGL((kernel), dim3(blocks_for((cells) / 2)), dim3(256), 0, as_stream(st), __VA_ARGS__); } \
+        else { constexpr int VEC = 1; hipLaunchKernelGGL((kernel), dim3(blocks_for(cells)), dim3(256), 0, as_stream(st), __VA_ARGS__); }            \
+        PDEHIP_HIP(hipGetLastError());                                                                                               \
+    } while (0)
+
+// The final sums of N interleaved columns of wave partials by ONE workgroup of 256 threads: thread i adds the slots i, i + 256, ... in
+// that order, then a tree over the 256 sums in LDS - the same order in every run.  Every thread returns with the sums.
+template <int N>
+__device__ __forceinline__ void sum_slots(const double *slots, int n, double (&out)[N])
+{
+    __shared__ double part[N][256];
+#pragma unroll
+    for (int q = 0; q < N; q++) out[q] = 0;
+    for (int i = threadIdx.x; i < n; i += 256)
+#pragma unroll
+        for (int q = 0; q < N; q++) out[q] = out[q] + slots[N * i + q];
+#pragma unroll
+    for (int q = 0; q < N; q++) part[q][threadIdx.x] = out[q];
+    __syncthreads();
+    for (int w = 128; w >= 1; w >>= 1) {
+        if ((int)threadIdx.x < w)
+#pragma unroll
+            for (int q = 0; q < N; q++) part[q][threadIdx.x] = part[q][threadIdx.x] + part[q][threadIdx.x + w];
+        __syncthreads();
+    }
+#pragma unroll
+    for (int q = 0; q < N; q++) out[q] = part[q][0];
+}
+// slots a one-workgroup kernel sums: what the last sweep announced, as far as the buffer holds it
+__device__ __forceinline__ int ctl_nslots(const CtlHead &h) { return h.nslots < h.capacity ? h.nslots : h.capacity; }
+
+// a control block read back through pinned memory: the one host synchronisation of a batch
+inline int read_ctl(void *host, void *pinned, const void *dev, size_t bytes, void *st)
+{
+    PDEHIP_HIP(hipMemcpyAsync(pinned, dev, bytes, hipMemcpyDeviceToHost, as_stream(st)));
+    PDEHIP_HIP(hipStreamSynchronize(as_stream(st)));
+    memcpy(host, pinned, bytes);
+    return 0;
+}
+
+}  // namespace pdehip

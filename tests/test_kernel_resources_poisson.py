@@ -11,8 +11,11 @@ import pytest
 
 from test_kernel_resources import LIB, LLVM_BIN, _kernel_metadata
 
+# every kernel of the solver: the loop both methods share, the kernels around a solve, the multigrid cycle
 OWN = ("poisson_update_kernel", "poisson_finish_kernel", "poisson_apply_kernel", "poisson_rhs_kernel", "poisson_reduce_kernel",
-       "poisson_check_kernel", "poisson_store_kernel", "poisson_shift_kernel", "poisson_sum_kernel", "poisson_init_kernel")
+       "poisson_check_kernel", "poisson_store_kernel", "poisson_shift_kernel", "poisson_sum_kernel", "poisson_init_kernel",
+       "poisson_mg_smooth0_kernel", "poisson_mg_sweep_kernel", "poisson_mg_restrict_kernel", "poisson_mg_prolong_kernel",
+       "poisson_mg_coarse_kernel", "poisson_mg_face_kernel", "poisson_mg_apply_kernel", "poisson_mg_open_kernel")
 
 
 def test_poisson_instances_have_no_scratch(tmp_path):
