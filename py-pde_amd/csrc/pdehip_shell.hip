@@ -305,7 +305,7 @@ int preload_shell_kernels()
     return 0;
 }
 
-// The last one to eight columns of every row behind a two-step sweep whose tiles cover whole chunks only (launch_euler2_tv, "open" rows):
+// The last one to eight columns of every row behind a two-step sweep whose tiles cover whole chunks only (e2plan::plan_tile, "open" rows):
 // the two layers of cells next to the upper face of the fastest axis, with the scalar conditions of the sweep (`a`: kernel axes).
 // `rows` (round 6, "open" columns of tiles): the same for the last one to seven ROWS of every plane - the two layers next to the upper face of the rows.
 int shell_open_rows(const NGrid &n, const LapArgs &la, int columns, int rows, hipStream_t st)

@@ -518,7 +518,7 @@ int rhs_sweep(Ops &ops, const pdehip_grid_t *g, const Geo &q, const pdehip_rhs_t
         if (!done && fuse_stage && out) {
             // The sweep itself is covered, its stage epilogue is not: on grids that need overlapping tiles (an odd row count, rows
             // that end inside a vector) cells are computed twice, so an epilogue that overwrites one of its own operands - the RK4
-            // update writes the new state over y - is refused (launch_euler2_tv).  Slope alone into `out` (every caller passes a
+            // update writes the new state over y - is refused (e2plan::plan_tile).  Slope alone into `out` (every caller passes a
             // free array, also for the kinds that do not store it), then the pointwise combination: what pdehip_rk4_step does.
             SLAB_TRY(ops.ch_fused(g, in, out, rhs->param, dt, euler, fc, fm, st, &done, xends(lower, upper), false, nullptr));
             if (done) return ops.combine(g, out, *sf, st);
