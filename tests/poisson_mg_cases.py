@@ -11,7 +11,7 @@ import numpy as np
 from helpers import host_faces
 from oracle import pde_oracle as O
 from pde_hip import _abi
-from poisson_cases import laplace_with_bcs
+from poisson_cases import CONVERGED, MAXITER, STATUS_NAMES, cg_loop, laplace_with_bcs
 
 
 def hierarchy(shape, max_levels=None, stop_cells: int = 512) -> list[tuple[int, ...]]:
@@ -170,27 +170,20 @@ class Cycle:
         return mat
 
 
-def mgcg(grid, bc, rhs: np.ndarray, rtol: float = 1e-10, maxiter: int = 200, singular: bool = False, **cycle_args):
-    """(-A) u = v - f by conjugate gradients preconditioned with the cycle; returns (u, iterations)."""
+def mgcg(grid, bc, rhs: np.ndarray, rtol: float = 1e-10, maxiter: int = 200, singular: bool = False, atol: float = 0.0, sums=None,
+         keep=None, **cycle_args):
+    """(-A) u = v - f by conjugate gradients preconditioned with the cycle: the loop of tests/poisson_cases.py (`cg_loop`) with
+    z = M r.  `sums=None`: returns (u, iterations) and raises when `maxiter` is reached (np.sum dot products); `sums="exact"` /
+    `"numpy"`: returns the `Trajectory` like `cg`, whatever the status."""
     m = Cycle(grid, bc, **cycle_args)
-    lv = m.levels[0]
     v = laplace_with_bcs(grid, bc, np.zeros(grid.shape))
-    r = v - np.asarray(rhs, dtype=float)
-    if singular:
-        r = r - r.mean()
-    x, p, q = np.zeros(grid.shape), np.zeros(grid.shape), np.zeros(grid.shape)
-    tol = rtol * np.linalg.norm(r)
-    gamma_prev = alpha_prev = 1.0
-    for it in range(maxiter + 1):
-        if np.linalg.norm(r) <= tol:
-            return (x - x.mean() if singular else x), it
-        z = m(r)
-        w = lv.minus_a(z)
-        gamma, delta = float((r * z).sum()), float((z * w).sum())
-        beta = gamma / gamma_prev if it else 0.0
-        alpha = gamma / (delta - beta * gamma / alpha_prev) if it else gamma / delta
-        p, q = z + beta * p, w + beta * q
-        x, r = x + alpha * p, r - alpha * q
-        gamma_prev, alpha_prev = gamma, alpha
-    msg = f"restated mgcg did not converge within {maxiter} iterations"
-    raise RuntimeError(msg)
+    traj = cg_loop(v, m.levels[0].minus_a, rhs, rtol, atol, maxiter, singular, sums or "numpy", m, keep if sums else ())
+    if sums:
+        return traj
+    if traj.status == MAXITER:
+        msg = f"restated mgcg did not converge within {maxiter} iterations"
+        raise RuntimeError(msg)
+    if traj.status != CONVERGED:
+        msg = f"restated mgcg ended with {STATUS_NAMES[traj.status]} after {traj.iterations} iterations"
+        raise RuntimeError(msg)
+    return traj.x, traj.iterations

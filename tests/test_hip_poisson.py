@@ -1,6 +1,7 @@
 """GPU tests of the Poisson solver on the mirror classes: the reference's golden solutions, residuals of large grids measured with the
 existing device Laplacian, fp32 and complex fields, determinism, independence of the batch size, iteration counts, the failure modes
-and the refusals.  On a library without the operator every test here fails."""
+and the refusals; the stop rule and the return statuses (tests/poisson_stop_cases.py); conditions given as expressions of the
+coordinates and of time.  On a library without the operator every test here fails."""
 
 from __future__ import annotations
 
@@ -8,6 +9,7 @@ import numpy as np
 import pytest
 
 import pde_hip
+import poisson_stop_cases as stop
 from helpers import GOLDEN, get_case, load_cases
 
 pytestmark = pytest.mark.gpu
@@ -206,3 +208,61 @@ def test_last_kernel_name_names_the_fused_sweep(backend):
     grid.make_operator("poisson_solver", {"value": 0.0}, backend=backend)(np.ones(grid.shape))
     name = _lib.get_lib().last_kernel_name().decode()
     assert "poisson_apply_kernel" in name and "r.r and r.w" in name, name
+
+
+# ---- stop rule and statuses (the preconditioned twins: tests/test_hip_poisson_mg.py) ------------------------------------------------
+def test_atol_stops_at_the_restatements_iteration(backend):
+    stop.check_atol(backend, "cg")
+
+
+def test_right_hand_side_of_the_zero_field_needs_no_iteration(backend):
+    stop.check_zero_iterations(backend, "cg")
+
+
+def test_nan_and_inf_are_a_status_and_the_operator_survives(backend):
+    stop.check_nonfinite(backend, "cg")
+
+
+def test_indefinite_system_breaks_down_at_the_restatements_iteration(backend):
+    stop.check_breakdown(backend, "cg")
+
+
+# ---- conditions given as expressions ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("method", ["cg", "mgcg"])
+def test_expression_conditions_equal_the_same_values_as_arrays(method, backend):
+    """Coefficients that are powers of two: the expression and the array hold the same bits whatever the order of the products."""
+    grid = pde_hip.CartesianGrid([[0, 4.0], [0, 6.0]], [32, 48])
+    y = np.asarray(grid.axes_coords[1])
+    as_expr = [[{"value_expression": "0.5 + 0.25*y"}, {"derivative_expression": "0.125*y"}], {"value": 0.0}]
+    as_arrays = [[{"value": 0.5 + 0.25 * y}, {"derivative": 0.125 * y}], {"value": 0.0}]
+    f = np.random.default_rng(31).uniform(-1, 1, grid.shape)
+    a = grid.make_operator("poisson_solver", as_expr, backend=backend, method=method)
+    b = grid.make_operator("poisson_solver", as_arrays, backend=backend, method=method)
+    assert np.array_equal(a(f), b(f)) and a.info == b.info and a.info["iterations"] > 0
+    u = pde_hip.ScalarField(grid, a(f))
+    assert np.linalg.norm(u.laplace(as_arrays).data - f) <= 1e-8 * np.linalg.norm(f)
+
+
+@pytest.mark.parametrize("method", ["cg", "mgcg"])
+def test_time_dependent_condition_is_refreshed_on_every_solve(method, backend):
+    """One operator, two times: each solve equals a fresh operator with the value of that time as a constant (the handle is rebuilt on
+    every solve, because the coefficient arrays - and with them whether the system is singular - may have changed)."""
+    grid = pde_hip.CartesianGrid([[0, 4.0], [0, 6.0]], [32, 48])
+    f = np.random.default_rng(32).uniform(-1, 1, grid.shape)
+    op = grid.make_operator("poisson_solver", [[{"value_expression": "0.5 + 0.25*t"}, {"derivative": 0.2}], {"value": 0.0}], backend=backend, method=method)
+    got = {t: op(f, args={"t": t}).copy() for t in (1.0, 3.0, 1.0)}
+    for t, value in ((1.0, 0.75), (3.0, 1.25)):
+        fresh = grid.make_operator("poisson_solver", [[{"value": value}, {"derivative": 0.2}], {"value": 0.0}], backend=backend, method=method)
+        assert np.array_equal(got[t], fresh(f)), t
+    assert not np.array_equal(got[1.0], got[3.0])
+    with pytest.raises(RuntimeError, match="Require value for `t`"):
+        op(f)
+
+
+def test_expression_that_reads_the_value_is_refused(backend):
+    """(No CPU twin: the refusal is made by `_Solver` after the expression table has uploaded its coefficient arrays, and the host shim
+    of the CPU tests has no Poisson entry points, so the operator is refused there before it gets that far.)"""
+    grid = pde_hip.UnitGrid([16, 16])
+    for bc in ({"value_expression": "value**2"}, {"derivative_expression": "0.1 - 0.3 * value**3"}):
+        with pytest.raises(NotImplementedError, match="not affine in the adjacent value: the problem is not linear"):
+            grid.make_operator("poisson_solver", [[bc, {"value": 0.0}], {"value": 0.0}], backend=backend)

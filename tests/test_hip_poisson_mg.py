@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import pde_hip
+import poisson_stop_cases as stop
 from helpers import GOLDEN, get_case, load_cases
 from poisson_mg_cases import Cycle, hierarchy
 
@@ -75,6 +76,14 @@ def test_laplace_golden_and_the_inconsistent_singular_case(backend):
     assert "Poisson problem could not be solved (Residual:" in str(err.value.__cause__)
 
 
+def ramp(m1, m2, a, b, c=0.0):
+    return a * np.linspace(0, 1, m1)[:, None] + b * np.linspace(0, 1, m2)[None, :] + c
+
+
+ARRAY_FACES3 = [[{"value": ramp(10, 36, 1.0, 0.5)}, {"type": "mixed", "value": ramp(10, 36, 0.3, 1.1, 0.2), "const": 0.1}],
+                [{"type": "mixed", "value": ramp(40, 36, 0.7, 0.2, 0.1), "const": ramp(40, 36, 0.1, 0.1)}, {"value": ramp(40, 36, 0.2, 0.9)}],
+                [{"derivative": ramp(40, 10, 0.4, 0.3)}, {"type": "mixed", "value": ramp(40, 10, 0.25, 1.3, 0.4), "const": 0.0}]]
+
 CYCLES = [
     ("1d-even", [[0, 3.0]], [1024], [False], [[{"value": 0.2}, {"derivative": 0.1}]], {}),
     ("1d-odd-no-coarsening", [[0, 3.0]], [777], [True], "periodic", {"mg_coarse": 5}),
@@ -85,6 +94,24 @@ CYCLES = [
     ("3d-faces", [[0, 1.0], [0, 0.5], [0, 2.0]], [24, 20, 32], [False, False, True], FACES3, {}),
     ("3d-one-sweep", [[0, 1.0], [0, 1.0], [0, 1.0]], [16, 16, 18], [False, True, False], [{"derivative": 0.0}, "periodic", {"value": 1.0}], {"mg_smooth": 1, "mg_coarse": 1}),
     ("3d-two-levels", [[0, 1.0], [0, 1.0], [0, 1.0]], [32, 32, 32], [False, False, False], {"value": 0.0}, {"mg_levels": 2, "mg_coarse": 3}),
+    # coefficient arrays on the faces of all three axes, every factor array from two different ramps (a transposed or mis-strided face
+    # shows); 40 x 10 x 36 -> 20 x 5 x 18 -> 10 x 5 x 9: the first transfer halves both axes of the faces of axis 1, the second only one
+    # axis of the faces of axes 0 and 2
+    ("3d-array-faces", [[0, 1.0], [0, 0.5], [0, 2.0]], [40, 10, 36], [False, False, False], ARRAY_FACES3, {}),
+    ("3d-array-faces-one-transfer", [[0, 1.0], [0, 0.5], [0, 2.0]], [40, 10, 36], [False, False, False], ARRAY_FACES3, {"mg_levels": 2, "mg_coarse": 4}),
+    # the last level 8 x 8 x 9 = 576 cells in LDS, every axis wrapping inside the one-workgroup kernel
+    ("3d-lds-periodic", [[0, 1.0], [0, 0.5], [0, 2.0]], [16, 16, 18], [True, True, True], "periodic", {"mg_levels": 2}),
+    ("3d-lds-mixed-periodic", [[0, 1.0], [0, 0.5], [0, 2.0]], [16, 16, 18], [True, False, True], ["periodic", [{"value": 0.5}, MIXED], "periodic"], {"mg_levels": 2, "mg_coarse": 7}),
+    # an axis of extent 2: periodic (both neighbours are the same cell) and between walls
+    ("3d-extent-2-periodic", [[0, 1.0], [0, 0.5], [0, 2.0]], [64, 2, 64], [False, True, False], [{"value": 0.5}, "periodic", {"derivative": 0.1}], {}),
+    ("3d-extent-2-walls", [[0, 1.0], [0, 0.5], [0, 2.0]], [64, 2, 64], [False, False, False], [{"value": 0.5}, [{"derivative": -0.2}, MIXED], {"derivative": 0.1}], {}),
+    ("2d-extent-2-periodic", [[0, 1.0], [0, 8.0]], [2, 64], [True, False], ["periodic", [{"value": 0.5}, MIXED]], {}),
+    ("2d-extent-2-periodic-fastest", [[0, 8.0], [0, 1.0]], [64, 2], [False, True], [[{"value": 0.5}, MIXED], "periodic"], {"mg_coarse": 6}),
+    # a 3-D last level above 1024 cells (12 x 10 x 16) with faces: one launch per sweep
+    ("3d-large-last-level", [[0, 1.0], [0, 0.5], [0, 2.0]], [24, 20, 32], [False, False, True], FACES3, {"mg_levels": 2, "mg_coarse": 5}),
+    # one sweep on a level in LDS: the loop over further sweeps runs zero times
+    ("2d-lds-one-sweep", [[0, 2.0], [0, 3.0]], [32, 24], [False, False], [[{"value": 0.5}, MIXED], [{"derivative": -0.2}, {"value": 2.0}]], {"mg_coarse": 1}),
+    ("1d-lds-one-sweep-one-level", [[0, 3.0]], [777], [True], "periodic", {"mg_coarse": 1}),
 ]
 
 
@@ -219,3 +246,48 @@ def test_runs_and_batch_sizes_give_equal_bits_and_the_plain_path_is_unchanged(ba
     assert np.array_equal(a, c) and auto.info["iterations"] == plain.info["iterations"] > runs[0][1]
     assert "poisson_apply_kernel" in _lib.get_lib().last_kernel_name().decode()
     assert rel_max(runs[0][0], a) < 1e-8
+
+
+@pytest.mark.parametrize("method", ["mgcg", "cg"])
+def test_factor_arrays_of_exact_ones_make_the_system_singular(method, backend):
+    """Neumann conditions given as arrays on every face: the library reads the factor arrays (all ones) from the device, finds the
+    system singular and returns the solution of mean zero."""
+    from pde_hip.device import DeviceArray
+
+    grid = pde_hip.CartesianGrid([[0, 1.0], [0, 0.5], [0, 2.0]], [40, 10, 36])
+    centred = lambda m1, m2, a, b: ramp(m1, m2, a, b) - ramp(m1, m2, a, b).mean()      # noqa: E731  (no net flux through a face)
+    bc = [[{"derivative": centred(10, 36, 0.4, 0.3)}, {"derivative": centred(10, 36, 0.1, -0.3)}], [{"derivative": centred(40, 36, 0.2, 0.1)}, {"derivative": np.zeros((40, 36))}],
+          [{"derivative": centred(40, 10, -0.2, 0.3)}, {"derivative": centred(40, 10, 0.5, 0.5)}]]
+    f = np.random.default_rng(12).uniform(-1, 1, grid.shape)
+    f -= f.mean()
+    op = grid.make_operator("poisson_solver", bc, backend=backend, method=method, rtol=1e-9)
+    info = backend.grid_info(grid, np.float64)
+    out = DeviceArray(info)
+    status = op.solver_for(None).solve(DeviceArray(info).set_valid(f, backend.stream), out)
+    assert status["singular"] and status["status"] == 0 and status["iterations"] > 0, status
+    got = out.get_valid(stream=backend.stream)
+    assert abs(got.mean()) < 1e-10
+    u = pde_hip.ScalarField(grid, got)
+    assert np.linalg.norm(u.laplace(bc).data - f) <= 1e-7 * np.linalg.norm(f)
+    # one factor that is not one: regular
+    bc[1][1] = {"type": "mixed", "value": np.where(np.arange(40 * 36).reshape(40, 36) == 777, 0.5, 0.0), "const": 0.0}
+    op = grid.make_operator("poisson_solver", bc, backend=backend, method=method, rtol=1e-9)
+    status = op.solver_for(None).solve(DeviceArray(info).set_valid(f, backend.stream), out)
+    assert not status["singular"], status
+
+
+# ---- stop rule and statuses: the twins of tests/test_hip_poisson.py ----------------------------------------------------------------------
+def test_atol_stops_at_the_restatements_iteration(backend):
+    stop.check_atol(backend, "mgcg")
+
+
+def test_right_hand_side_of_the_zero_field_needs_no_iteration(backend):
+    stop.check_zero_iterations(backend, "mgcg")
+
+
+def test_nan_and_inf_are_a_status_and_the_operator_survives(backend):
+    stop.check_nonfinite(backend, "mgcg")
+
+
+def test_indefinite_system_breaks_down_near_the_restatements_iteration(backend):
+    stop.check_breakdown(backend, "mgcg")

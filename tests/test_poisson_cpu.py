@@ -1,6 +1,8 @@
 """CPU checks of the Poisson solver: a dense numpy restatement (tests/poisson_cases.py) reproduces the reference's golden solutions;
 the decisions taken on the host - singular systems, refused conditions, the `method` argument, the operator without conditions - are
-tested on the face tables without a device; a library without the entry points (the host shim) refuses the operator and names them."""
+tested on the face tables without a device; a library without the entry points (the host shim) refuses the operator and names them.
+The restated loop (`cg`) reproduces the dense solutions, ends in breakdown on an indefinite system, and keeps the tolerances of the
+device tests (tests/test_hip_poisson_trajectory.py) with its own two summation modes."""
 
 from __future__ import annotations
 
@@ -12,7 +14,7 @@ import refpath
 import shimlib
 from helpers import GOLDEN, get_case, host_faces, load_cases
 from pde_hip import _abi, poisson
-from poisson_cases import NotSolved, dense_solve, laplace_with_bcs, make_grid
+from poisson_cases import BREAKDOWN, CONVERGED, INDEFINITE, NotSolved, cg, dense_solve, laplace_with_bcs, make_grid
 
 NPZ = np.load(GOLDEN / "poisson.npz", allow_pickle=False)
 NEW = ["poisson_create", "poisson_solve", "poisson_destroy"]
@@ -147,3 +149,46 @@ def test_host_shim_refuses_the_operator_and_names_the_entry_points():
             grid.make_operator_no_bc("poisson_solver", backend="hip")
         with pytest.raises(NotImplementedError):                                  # inside expressions it stays refused
             pde_hip.PDE({"c": "poisson_solver(c)"}).evolution_rate(pde_hip.ScalarField(grid, 1.0))
+
+
+# ---- the restated loop behind the device tests that compare iteration by iteration ------------------------------------------------
+def indefinite_case():
+    grid = pde_hip.UnitGrid(INDEFINITE["shape"])
+    return grid, INDEFINITE["bc"], np.random.default_rng(INDEFINITE["seed"]).uniform(-1, 1, grid.shape)
+
+
+@pytest.mark.parametrize("cid", [c for c in DENSE if not get_case(NPZ, c).get("raises")])
+def test_restated_cg_reproduces_the_dense_solutions(cid):
+    case = get_case(NPZ, cid)
+    grid = make_grid(case)
+    singular = poisson.is_singular(host_faces(grid.get_boundary_conditions(case["bc"])).c, grid.num_axes)
+    want = dense_solve(grid, case["bc"], NPZ[f"{cid}/rhs"])
+    for sums in ("exact", "numpy"):
+        traj = cg(grid, case["bc"], NPZ[f"{cid}/rhs"], rtol=1e-12, maxiter=poisson.default_maxiter(grid.shape), singular=singular, sums=sums, keep=())
+        assert traj.status == CONVERGED and 0 < traj.iterations == len(traj.scalars)
+        assert np.abs(traj.x - want).max() <= 1e-8 * max(1.0, np.abs(want).max())
+        assert np.abs(traj.x - NPZ[f"{cid}/solution"] + (NPZ[f"{cid}/solution"].mean() if singular else 0.0)).max() <= 1e-8 * max(1.0, np.abs(want).max())
+
+
+def test_restated_cg_breaks_down_on_an_indefinite_system():
+    from poisson_cases import matrix_and_vector
+
+    grid, bc, f = indefinite_case()
+    assert host_faces(grid.get_boundary_conditions(bc)).c[0].factor1 > 2
+    assert np.linalg.eigvalsh(-matrix_and_vector(grid, bc)[0]).min() < 0
+    for sums in ("exact", "numpy"):
+        traj = cg(grid, bc, f, rtol=1e-10, maxiter=100, sums=sums)
+        assert traj.status == BREAKDOWN and traj.iterations == 1 and len(traj.iterates) == 1
+
+
+def test_trajectory_tolerances_hold_for_the_restatement_itself():
+    import poisson_trajectory_cases as T
+
+    assert set(T.TOL) == {c["id"] for c in T.CASES}
+    T.check_tolerances("cg")      # (the preconditioned cases: tests/test_poisson_mg_cpu.py)
+
+
+def test_both_summation_modes_need_the_same_iterations():
+    import poisson_trajectory_cases as T
+
+    T.check_equal_iteration_counts("cg")

@@ -139,3 +139,32 @@ def test_host_shim_refuses_the_method_and_names_the_entry_points():
                 grid.make_operator("poisson_solver", {"value": 0.0}, backend="hip", method="mgcg")
         finally:
             lib.missing |= plain
+
+
+def test_trajectory_tolerances_hold_for_the_restated_mgcg():
+    """The preconditioned cases of tests/test_hip_poisson_trajectory.py (the checks: tests/poisson_trajectory_cases.py)."""
+    import poisson_trajectory_cases as T
+
+    T.check_tolerances("mgcg")
+
+
+def test_both_summation_modes_need_the_same_mgcg_iterations():
+    import poisson_trajectory_cases as T
+
+    T.check_equal_iteration_counts("mgcg")
+
+
+def test_mgcg_returns_a_trajectory_like_cg():
+    grid = small_grid([8, 6], [False, False])
+    bc = SMALL[3][3]
+    f = np.random.default_rng(2).uniform(-1, 1, grid.shape)
+    u, iters = mgcg(grid, bc, f, rtol=1e-10, stop_cells=8)
+    traj = mgcg(grid, bc, f, rtol=1e-10, stop_cells=8, sums="numpy")
+    assert traj.status == 0 and traj.iterations == iters == len(traj.scalars) == len(traj.iterates)
+    assert np.array_equal(traj.x, u) and np.array_equal(traj.iterates[-1], u)
+    short = mgcg(grid, bc, f, rtol=1e-10, maxiter=2, stop_cells=8, sums="exact")
+    assert short.status == 1 and short.iterations == 2 and np.abs(short.iterates[1] - traj.iterates[1]).max() <= 1e-12 * np.abs(u).max()
+    with pytest.raises(RuntimeError, match="did not converge within 2"):
+        mgcg(grid, bc, f, rtol=1e-10, maxiter=2, stop_cells=8)
+    with pytest.raises(RuntimeError, match="ended with a non-finite scalar after 0 iterations"):      # other statuses keep their name
+        mgcg(grid, bc, np.where(f > 0.9, np.nan, f), rtol=1e-10, stop_cells=8)
