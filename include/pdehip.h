@@ -786,6 +786,43 @@ int pdehip_poisson_set_multigrid(void *handle, pdehip_poisson_mg_t *opts);
  * written; they may be the same array).  Uses the work vectors of the handle: not while a solve on it is in flight. */
 int pdehip_poisson_precondition(void *handle, const void *r_full, void *z_full, void *stream);
 
+/* ---- linear interpolation on the device (optional entry points; the ABI version stays 8) -----------------------------------------
+ * Replaces `make_interpolation_axis_data` and `make_single_interpolator` (pde/backends/numba/grids.py:102-190, :193-347) behind
+ * `BackendBase.make_interpolator` (pde/backends/base.py:606-632, numba twin pde/backends/numba/backend.py:895-988), operation by
+ * operation: per axis `c_l, d_l = divmod((coord - lo) / dx - 0.5, 1.0)` by the rule of CPython's float divmod, the reference's
+ * branches with its inequalities (periodic: wrap; valid data only: bulk / one-sided upper / one-sided lower; with_ghost_cells:
+ * the bulk rule on [-0.5, size - 0.5]), weights below 1e-15 set to 0, the 2 / 4 / 8 term sum left to right.  Weights and sums are
+ * fp64 for fp32 fields too, rounded once at the store.  `data_full` is a full array in the device layout (pdehip_layout) in BOTH
+ * modes: "valid data only" reads its interior with the one-sided branches (an index of -1, which the divmod rule yields for a tiny
+ * negative quotient, reads the last cell like `data[..., -1]`, with weight 0).  `ncomp` components are done in one launch (complex
+ * data: planar pairs, each part with the same real weights).  `periodic` and `lo` are HOST arrays of `ndim` entries
+ * (grid.periodic, grid.axes_bounds[a][0]).
+ *
+ * Points out of bounds (grids.py:156, :170, :251-256; a coordinate that is not finite counts as out of bounds): with `fill`
+ * (DEVICE array of `ncomp` doubles) that value is stored; without (NULL) nothing is stored for the point and it is counted into
+ * `oob_count` (DEVICE uint64, added to - zero it before).  No assert, no trap: the host raises `DomainError`.
+ *
+ * pdehip_interpolate_points: `points` = (npoints, ndim) fp64 on the device, `out` = (ncomp, npoints) in the grid's dtype.  One thread
+ * per point, grid-stride, 64-bit offsets. */
+int pdehip_interpolate_points(const pdehip_grid_t *g, int ncomp, const int *periodic_host, const double *lo_host, int with_ghost_cells,
+                              const void *data_full, const double *points, int64_t npoints, const double *fill, void *out,
+                              void *oob_count, void *stream);
+/* pdehip_interpolate_to_grid: the points are the cell centres of another Cartesian grid (`ScalarField.interpolate_to_grid`,
+ * pde/fields/scalar.py:468; DataFieldBase.interpolate_to_grid pde/fields/datafield_base.py:703-733), so support cells and weights are
+ * separable: a small kernel fills per-axis tables (c_li, c_hi, w_l, w_h, in-bounds flag for every target index of every axis) from
+ * `dst_coords` (DEVICE, the target's grid.axes_coords one axis after the other), the main kernel walks the target's rows along
+ * the fastest axis and writes the interior of the full array `dst_full` (its ghost cells are left alone).  `tables`: DEVICE
+ * workspace of 40 bytes per entry of `dst_coords`.  Same arithmetic and term order as pdehip_interpolate_points: equal bits. */
+int pdehip_interpolate_to_grid(const pdehip_grid_t *src, int ncomp, const int *periodic_host, const double *src_lo_host, int with_ghost_cells,
+                               const void *src_full, const pdehip_grid_t *dst, const double *dst_coords, const double *fill,
+                               void *dst_full, void *tables, void *oob_count, void *stream);
+/* Edge and corner ghost cells the way `BoundariesList.set_ghost_cells(..., set_corners=True)` fills them
+ * (pde/grids/boundaries/axes.py:458-501; used by `field.interpolate(point, bc=...)`, pde/fields/datafield_base.py:690-693): call
+ * AFTER pdehip_set_ghost_cells on the same stream.  2-D: corner = (d[nxt(i), j] + d[i, nxt(j)]) / 2; 3-D: the interior cells of the
+ * twelve edges the same way from the two adjacent face ghost cells, then corner = (sum of the three adjacent edge cells) / 3; in the
+ * field's own type, like numpy.  1-D grids: nothing to do.  pdehip_set_ghost_cells itself is unchanged. */
+int pdehip_set_ghost_corners(const pdehip_grid_t *g, int ncomp, void *data_full, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,7 @@ from .backend import HipBackend, get_backend
 from .boundaries import BoundariesList
 from .fields import FieldCollection, ScalarField, Tensor2Field, VectorField
 from .grids import CartesianGrid, UnitGrid
+from .interpolation import interpolate_to_grid
 from .pdes import (PDE, AllenCahnPDE, CahnHilliardPDE, DiffusionPDE, KleinGordonPDE, KPZInterfacePDE, KuramotoSivashinskyPDE,
                    SwiftHohenbergPDE, WavePDE)
 from .poisson import solve_laplace_equation, solve_poisson_equation
@@ -52,6 +53,7 @@ __all__ = [
     "UnitGrid",
     "VectorField",
     "get_backend",
+    "interpolate_to_grid",
     "solve_laplace_equation",
     "solve_poisson_equation",
 ]

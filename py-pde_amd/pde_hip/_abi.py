@@ -356,6 +356,10 @@ OPTIONAL_PROTOTYPES: dict[str, list] = {
     # ... preconditioned by a multigrid V-cycle (method "mgcg")
     "poisson_set_multigrid": [_vp, C.POINTER(PoissonMg)],
     "poisson_precondition": [_vp, _vp, _vp, _vp],
+    # linear interpolation at points / onto another grid, edge and corner ghost cells (csrc/pdehip_interp.hip)
+    "interpolate_points": [_pg, _i, C.POINTER(_i), _pd, _i, _vp, _vp, _i64, _vp, _vp, _vp, _vp],
+    "interpolate_to_grid": [_pg, _i, C.POINTER(_i), _pd, _i, _vp, _pg, _vp, _vp, _vp, _vp, _vp, _vp],
+    "set_ghost_corners": [_pg, _i, _vp, _vp],
 }
 
 

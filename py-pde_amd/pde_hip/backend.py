@@ -5,8 +5,8 @@
 ``register_operator`` / ``get_operator_info`` (``:256-376``), ``make_operator_no_bc``
 (``:482-521``), ``make_operator`` (``:523-565``), ``make_ghost_cell_setter`` /
 ``make_valid_data_setter`` / ``make_full_data_setter`` (``:378-429``), ``_apply_operator``
-(``:239-254``), ``numpy_to_native`` / ``native_to_numpy`` (``:186-205``), ``make_pde_rhs``
-(``:634-651``) and ``make_stepper`` (``:728-755``).
+(``:239-254``), ``numpy_to_native`` / ``native_to_numpy`` (``:186-205``), ``make_interpolator`` (``:606-632``,
+``pde_hip/interpolation.py``), ``make_pde_rhs`` (``:634-651``) and ``make_stepper`` (``:728-755``).
 
 The mixin only duck-types grids, boundary conditions, PDEs and solvers, so the same code
 serves (a) the stand-alone mirror classes of this package and (b) real py-pde objects when the
@@ -56,10 +56,11 @@ from .evaluation import _ExpressionEvaluation  # noqa: E402,F401
 from .resident import ResidentState, _config_get, _make_synced_class  # noqa: E402,F401
 from .operators_glue import _NONLINEAR_OPERATORS, OperatorGlueMixin  # noqa: E402,F401
 from .noise_hooks import NoiseHookMixin  # noqa: E402
+from .interpolation import InterpolationMixin  # noqa: E402
 from .steppers import StepperMixin  # noqa: E402
 
 
-class HipBackendMixin(OperatorGlueMixin, RhsPlanningMixin, NoiseHookMixin, StepperMixin):
+class HipBackendMixin(OperatorGlueMixin, InterpolationMixin, RhsPlanningMixin, NoiseHookMixin, StepperMixin):
     """Implementation shared by the stand-alone and the py-pde-plugin backend classes."""
 
     implementation = "hip"

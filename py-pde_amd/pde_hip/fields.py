@@ -83,8 +83,9 @@ class DataFieldBase:
         return cls(grid, np.array(data), label=label, dtype=dtype)
 
     # --- operators ------------------------------------------------------------------------------------
-    def set_ghost_cells(self, bc, *, args=None, backend="hip") -> None:
-        """Set the ghost cells of the host array (through the device ghost-cell kernel)."""
+    def set_ghost_cells(self, bc, *, set_corners: bool = False, args=None, backend="hip") -> None:
+        """Set the ghost cells of the host array (through the device ghost-cell kernel); ``set_corners``: edges and corners too
+        (fields/datafield_base.py:827-860, grids/boundaries/axes.py:475-495)."""
         from .backend import get_backend
         from .device import DeviceArray
 
@@ -92,8 +93,31 @@ class DataFieldBase:
         bcs = self.grid.get_boundary_conditions(bc, rank=self.rank)
         dev = DeviceArray(b.grid_info(self.grid, self.dtype), (self.grid.dim,) * self.rank)
         dev.set_hostfull(self._data_full, b.stream)
-        b.make_ghost_cell_setter(bcs)(dev, args=args)
+        b.make_ghost_cell_setter(bcs, set_corners=set_corners)(dev, args=args)
         self._data_full[...] = dev.get_hostfull(b.stream)
+
+    # --- interpolation (fields/datafield_base.py:631-733, fields/scalar.py:468) ------------------------------------------
+    @property
+    def data_shape(self) -> tuple[int, ...]:
+        return (self.grid.dim,) * self.rank
+
+    def make_interpolator(self, *, fill=None, with_ghost_cells: bool = False, backend="hip"):
+        """``interpolator(point, data=None)`` on the device (``HipBackendMixin.make_interpolator``)."""
+        from .backend import get_backend
+
+        return get_backend(backend).make_interpolator(self, fill=fill, with_ghost_cells=with_ghost_cells)
+
+    def interpolate(self, point, *, bc=None, fill=None, backend="hip"):
+        """Values at points in grid coordinates; with ``bc`` the conditions are imposed first, edge and corner ghost cells included."""
+        from .backend import get_backend
+
+        return get_backend(backend).interpolate_field(self, point, bc=bc, fill=fill)
+
+    def interpolate_to_grid(self, grid, *, bc=None, fill=None, label=None, backend="hip"):
+        """This field on another Cartesian grid (a field of the same class); other target grids are refused."""
+        from .backend import get_backend
+
+        return get_backend(backend).interpolate_to_grid(self, grid, bc=bc, fill=fill, label=label)
 
     def apply_operator(self, operator: str, bc, out=None, *, label=None, args=None, backend="hip", **kwargs):
         """Apply a (differential) operator with BCs (fields/datafield_base.py:900-963)."""

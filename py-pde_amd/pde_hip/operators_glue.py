@@ -30,8 +30,10 @@ _NONLINEAR_OPERATORS = frozenset({"gradient_squared"})
 class OperatorGlueMixin:
     """The operator-facing methods of :class:`~pde_hip.backend.HipBackendMixin`."""
 
-    def make_ghost_cell_setter(self, bcs):
-        """``f(data_full, args=None)`` — one fused kernel for all faces.
+    def make_ghost_cell_setter(self, bcs, *, set_corners: bool = False):
+        """``f(data_full, args=None)`` — one fused kernel for all faces.  ``set_corners=True``: the edge and corner ghost cells are
+        filled afterwards like ``BoundariesList.set_ghost_cells(..., set_corners=True)`` does (pde/grids/boundaries/axes.py:475-495;
+        ``pdehip_set_ghost_corners``) - what ``field.interpolate(point, bc=...)`` reads next to two or three walls.
 
         ``data_full`` is a :class:`DeviceArray` (the normal case inside steppers and operators) or, like the reference's
         setters (``pde/backends/numba/backend.py:342-404``), a host full array (``field._data_full``) that is updated in
@@ -53,6 +55,11 @@ class OperatorGlueMixin:
             if key not in tables:
                 tables[key] = make_face_setter(self, bcs, key)
             tables[key](data_full, args)
+            if set_corners:
+                if not self._lib.has("set_ghost_corners"):
+                    msg = "hip backend: the loaded library has no interpolation kernels (pdehip_set_ghost_corners)"
+                    raise NotImplementedError(msg)
+                self._lib.set_ghost_corners(data_full.info.ref, data_full.ncomp, data_full.ptr, self.stream)
 
         return ghost_cell_setter
 
