@@ -176,6 +176,9 @@ bool bcprog_second_set(void *handle, const double *const_arr, const double **c2,
 int bcprog_run_pair(void *handle, double t0, double t1, void *stream);
 int euler2_with_input_bcs(const pdehip_grid_t *g, const void *in, void *out, double s1, double s2,
                           const pdehip_bc_face_t *faces, void *stream, bool *done, int xplain = 0, bool dry_run = false, int ends = 0);
+// four Euler steps of the diffusion equation in one sweep (all-periodic fp64 3-D grids: pdehip_euler4_plan.h); *done as above
+int euler4_with_input_bcs(const pdehip_grid_t *g, const void *in, void *out, double s1, double s2, const pdehip_bc_face_t *faces,
+                          bool const_faces, void *stream, bool *done);
 // two Euler steps of the diffusion equation on a box of a larger array with two real halo layers on the cut axes (pdehip_ops.hip)
 int euler2_box(const pdehip_grid_t *g_box, const pdehip_bc_face_t *faces, const int *cut3, const void *in_ext, void *out_ext, double s1,
                double s2, void *stream, bool *done, bool dry_run = false, const long *lo3 = nullptr, const long *n3 = nullptr);

@@ -36,6 +36,10 @@ int launch_euler2(const NGrid &n, const void *in, void *out, double s1, double s
 {
     return PDEHIP_PICK(launch_euler2(n, in, out, s1, s2, fg, xplain, st, done, dry_run, ends, m2, fg1, gamma, plan, stage, yzplain));
 }
+int launch_euler4(const NGrid &n, const void *in, void *out, double s1, double s2, const InputBCs &fg, bool const_faces, hipStream_t st, bool *done)
+{
+    return PDEHIP_PICK(launch_euler4(n, in, out, s1, s2, fg, const_faces, st, done));
+}
 int tile2d_max_steps(int mode) { return exactv::tile2d_max_steps(mode); }
 int plan_tile2d(const NGrid &n, const void *in, void *out, int mode, double s1, double s2, double gamma, const InputBCs &fc, const InputBCs *fm,
                 int nsteps, Tile2Args *args, unsigned *nblocks, int *tile_columns, bool *done)
@@ -52,6 +56,7 @@ bool force_generic_kernels() { return exactv::force_generic_kernels(); }
 int preload_stencil_kernels() { PDEHIP_TRY(exactv::preload_stencil_kernels()); return fastv::preload_stencil_kernels(); }
 int preload_e2_kernels() { PDEHIP_TRY(exactv::preload_e2_kernels()); return fastv::preload_e2_kernels(); }
 int preload_t2_kernels() { PDEHIP_TRY(exactv::preload_t2_kernels()); return fastv::preload_t2_kernels(); }
+int preload_e4_kernels() { PDEHIP_TRY(exactv::preload_e4_kernels()); return fastv::preload_e4_kernels(); }
 
 }  // namespace pdehip
 

@@ -1,0 +1,139 @@
+// pdehip_march4.inc - four Euler steps of the diffusion equation per sweep, fp64, 3-D, every axis periodic:
+//     out = E(E(E(E(in)))),   E(u) = u + s2 * (s1 * laplace(u))          pde/solvers/euler.py:172-175
+// The 3-D counterpart of pdehip_tile2d.inc (time levels in LDS) with the march of pdehip_march2.inc: one read and one write of the field per
+// FOUR steps.  Included inside namespace pdehip::exactv / pdehip::fastv by pdehip_kernels_e4.hip; geometry: pdehip_euler4_plan.h.
+//
+// A workgroup owns TY x TZ outputs (rows x fastest axis) and marches along axis 0 over an x-chunk of `lx` planes.  Level L (1 ... 4) is
+// evaluated on the tile grown by 4 - L cells per side and on the chunk grown by 4 - L planes per end: the halo is recomputed, neighbouring
+// workgroups read the same input lines (from L2).  Periodic wraps are resolved in the load addresses: rows and columns once, planes per phase.
+//
+// A thread owns the same patch of PY rows x 2 cells at every level and keeps, for each of the levels 0 ... 3, its own cells of three
+// consecutive planes in registers.  Neighbours inside the patch come from those registers; the others from the LDS copy of the level's middle
+// plane.  The levels run skewed: iteration i (local planes count from the first loaded one) computes
+//     level 1 at plane i + 1,   level 2 at plane i,   level 3 at plane i - 1,   level 4 at plane i - 2   (stored from i = 6 on)
+// between two barriers: every thread first writes the middle plane of its four register levels to LDS.  The loop is unrolled three times so
+// that the rotation of the plane buffers is a renaming (like euler2_body).  Every thread executes every barrier: halo patches skip stores,
+// nothing else, and the trip count depends on the workgroup alone.  What the first iterations compute from planes that do not exist yet
+// (zeros) never reaches a stored cell: level L at plane p reads level L - 1 at p - 1 ... p + 1 only.
+//
+// Per cell the arithmetic is `laplace` + `update` of pdehip_march2.inc (cartesian.py:220-227) in the same order: bit-identical to four single
+// steps in the exact build.
+template <typename T, int M2>
+__global__ void __launch_bounds__(e4plan::THREADS) euler4_kernel(const LapArgs a)
+{
+    static_assert(sizeof(T) == 8 && (M2 == E2_DIFFUSION || M2 == E2_DIFFUSION_UNIT), "fp64 diffusion only");
+    using namespace e4plan;
+    typedef typename VecT<T, 2>::type V;
+    constexpr int LP = LPITCH, PLANE = LROWS * LPITCH;
+    __shared__ __attribute__((aligned(16))) T lds[LEVELS * PLANE];
+
+    // the threads behind the last patch repeat patch 0: a halo patch (the same values written twice, nothing stored)
+    const int tid = (int)threadIdx.x < PATCHES ? (int)threadIdx.x : 0;
+    const int py = tid / NPZ, pz = tid - py * NPZ;
+    const int ly = py * PY, lz = 2 * pz;                       // first row / column of the patch in the region of level 0
+    const bool owner = ly >= HALO && ly < HALO + TY && lz >= HALO && lz < HALO + TZ;   // (HALO % PY == 0: a patch is output or halo as a whole)
+
+    const long w = xcd_swizzle((long)blockIdx.x, a.nblocks);
+    const long tiles = a.nty * a.ntz;
+    const long xc = w / tiles, tile = w - xc * tiles;
+    const long ty = tile / a.ntz, tz = tile - ty * a.ntz;
+    const long x0 = xc * a.xstride;
+    const int lx = (int)((a.n0 - x0 < (long)a.lx) ? a.n0 - x0 : (long)a.lx);
+    auto wrap = [](long i, long n) { return i < 0 ? i + n : (i >= n ? i - n : i); };   // (n >= the tile / 16 planes: one wrap is enough)
+
+    long roff[PY];   // element offset of the patch's rows in a plane
+    const long zc = wrap(tz * TZ - HALO + lz, a.n2);           // even: a patch never straddles the wrap
+#pragma unroll
+    for (int r = 0; r < PY; r++) roff[r] = a.off + wrap(ty * TY - HALO + ly + r, a.n1) * a.p1 + zc;
+    const T *in = (const T *)a.in;
+    T *out = (T *)a.out;
+    auto plane_src = [&](int q) { return wrap(x0 - HALO + q, a.n0) * a.p0; };   // local plane q of level 0
+    const int qlast = lx + 2 * HALO - 1;
+    auto load_plane = [&](int q, V (&dst)[PY]) {
+        const long po = plane_src(q < qlast ? q : qlast);      // (the prefetch behind the last plane repeats it)
+#pragma unroll
+        for (int r = 0; r < PY; r++) dst[r] = PDEHIP_LDV((const V *)(in + po + roff[r]));
+    };
+
+    const int lbase = (ly + 1) * LP + lz + 2;   // the patch's first cell in an LDS plane
+
+    auto update = [&](double xm, double xp, double up, double dn, double left, double right, double cen) {
+        const double vm = 2 * cen;
+        if (M2 == E2_DIFFUSION_UNIT) {   // all scales are exactly 1.0
+            const double ex = xm - vm + xp, ey = up - vm + dn, ez = left - vm + right;
+            return cen + a.s2 * (ex + ey + ez);
+        }
+        const double ex = (xm - vm + xp) * a.sx;
+        const double ey = (up - vm + dn) * a.sy;
+        const double ez = (left - vm + right) * a.sz;
+        return epilogue<LAP_EULER>(ex + ey + ez, cen, cen, a.s1, a.s2, a.gamma);
+    };
+    // one level up: the plane of `mid` at the next level, from the thread's cells of three planes and the LDS copy of the middle one
+    auto level = [&](const V (&old)[PY], const V (&mid)[PY], const V (&nw)[PY], const T *lp, V (&res)[PY]) {
+        const T *p = lp + lbase;
+        const V above = *(const V *)(p - LP), below = *(const V *)(p + PY * LP);
+#pragma unroll
+        for (int r = 0; r < PY; r++) {
+            const double left = p[r * LP - 1], right = p[r * LP + 2];
+            const V up = r == 0 ? above : mid[r > 0 ? r - 1 : 0], dn = r == PY - 1 ? below : mid[r < PY - 1 ? r + 1 : r];
+            res[r][0] = update(old[r][0], nw[r][0], up[0], dn[0], left, mid[r][1], mid[r][0]);
+            res[r][1] = update(old[r][1], nw[r][1], up[1], dn[1], mid[r][0], right, mid[r][1]);
+        }
+    };
+
+    // R[L][s]: level L, plane slot s; slot of local plane j = j mod 3
+    V R[LEVELS][3][PY], pre[PY];
+#pragma unroll
+    for (int l = 0; l < LEVELS; l++)
+#pragma unroll
+        for (int s = 0; s < 3; s++)
+#pragma unroll
+            for (int r = 0; r < PY; r++) R[l][s][r] = V{0, 0};
+    load_plane(0, R[0][0]);
+    load_plane(1, R[0][1]);
+    load_plane(2, R[0][2]);
+
+    // iteration i, i mod 3 == K: level 0 holds planes i, i + 1, i + 2 in slots K, K + 1, K + 2 (mod 3); level L the planes L lower
+    auto phase = [&](int i, auto kc) {
+        constexpr int K = decltype(kc)::value;
+        load_plane(i + 3, pre);   // needed at the next iteration
+#pragma unroll
+        for (int l = 0; l < LEVELS; l++) {   // the middle planes: level 0 plane i + 1, level 1 plane i, ...
+            const V (&mid)[PY] = R[l][(K + 4 - l) % 3];
+#pragma unroll
+            for (int r = 0; r < PY; r++) *(V *)(lds + l * PLANE + lbase + r * LP) = mid[r];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int l = 0; l < LEVELS; l++) {
+            // level l holds planes (i - l, i + 1 - l, i + 2 - l); level l + 1 gets plane i + 1 - l, in the slot of its plane i - 2 - l
+            const V (&old)[PY] = R[l][(K + 3 - l) % 3];
+            const V (&mid)[PY] = R[l][(K + 4 - l) % 3];
+            const V (&nw)[PY] = R[l][(K + 5 - l) % 3];
+            if (l < LEVELS - 1) {
+                level(old, mid, nw, lds + l * PLANE, R[l + 1][(K + 4 - l) % 3]);
+            } else {
+                V res[PY];
+                level(old, mid, nw, lds + l * PLANE, res);
+                const int q = i - 2;   // the local plane of level 4: output plane x0 + q - HALO
+                if (owner && q >= HALO) {
+                    const long po = (x0 + q - HALO) * a.p0;
+#pragma unroll
+                    for (int r = 0; r < PY; r++) __builtin_nontemporal_store(res[r], (V *)(out + po + roff[r]));
+                }
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < PY; r++) R[0][K][r] = pre[r];   // plane i is dead: plane i + 3 takes its slot
+    };
+    const int iend = lx + 2 * HALO - 3;   // the last iteration: level 4 at plane lx + HALO - 1
+    for (int i = 0;; i += 3) {
+        phase(i, std::integral_constant<int, 0>());
+        if (i + 1 > iend) break;
+        phase(i + 1, std::integral_constant<int, 1>());
+        if (i + 2 > iend) break;
+        phase(i + 2, std::integral_constant<int, 2>());
+        if (i + 3 > iend) break;
+    }
+}

@@ -708,6 +708,20 @@ int euler2_with_input_bcs(const pdehip_grid_t *g, const void *in, void *out, dou
     return launch_euler2(n, in, out, s1, s2, fg, xplain, as_stream(stream), done, dry_run, ends);
 }
 
+// four Euler steps per sweep (pdehip_march4.inc); `const_faces`: what e4plan::Query says.  *done = false: nothing launched
+int euler4_with_input_bcs(const pdehip_grid_t *g, const void *in, void *out, double s1, double s2, const pdehip_bc_face_t *faces,
+                          bool const_faces, void *stream, bool *done)
+{
+    *done = false;
+    NGrid n;
+    PDEHIP_TRY(norm_grid(g, &n));
+    if (!in || !out || !faces) PDEHIP_FAIL(E_VALUE, "euler4: NULL pointer");
+    if (n.ndim != 3) return 0;
+    InputBCs fg;
+    if (!faces_to_input_bcs(n, faces, &fg)) return 0;
+    return launch_euler4(n, in, out, s1, s2, fg, const_faces, as_stream(stream), done);
+}
+
 // Two Euler steps on a BOX of a larger array (fast block decomposition, pdehip_block2_loops.h).  `g_box`: the own cells of the rank;
 // `in_ext` / `out_ext`: full arrays of the grid two cells larger along the first two axes (own cell (0, 0, 0) = its interior cell
 // (1, 1, 0)), i.e. two halo planes / rows on either side; along the fastest axis the two halo cells sit in the row padding.  Cut axes

@@ -197,6 +197,7 @@ int pdehip_set_device(int device)
         PDEHIP_TRY(preload_stencil_kernels());
         PDEHIP_TRY(preload_e2_kernels());
         PDEHIP_TRY(preload_t2_kernels());
+        PDEHIP_TRY(preload_e4_kernels());
         PDEHIP_TRY(preload_shell_kernels());
         loaded = true;
     }

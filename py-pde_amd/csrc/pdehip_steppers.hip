@@ -6,6 +6,7 @@
 //   Cahn–Hilliard Euler    : ghosts + ch_mu (1r+1w) + ghosts + laplace_euler(mu; y=c) (2r+1w) = 5 values
 //   RK stage               : lincomb (1+j reads, 1 write) + rhs_scaled; diffusion: ONE sweep per stage (rhs_stage)
 #include "pdehip_common.h"
+#include "pdehip_euler4_plan.h"
 #include "pdehip_fixedpoint.h"
 
 using namespace pdehip;
@@ -39,6 +40,7 @@ struct GraphKey {
     void *buf[8];   // every array the captured launches touch (Euler: the two ping-pong buffers; RK4: y and the work arrays)
     double dt;
     int kind;       // 0 Euler block, 1 RK4 block
+    int euler4;     // PDEHIP_EULER4 as read at this call (e4plan::knob_from_env): a graph captured under one setting is not replayed under another
 };
 struct GraphEntry {
     GraphKey key;
@@ -204,6 +206,10 @@ int pdehip_euler_run(const pdehip_grid_t *g, const pdehip_rhs_t *rhs, void *buf_
     long ncells = 1;
     for (int q = 0; q < g->ndim; q++) ncells *= g->shape[q];
     bool tile_ok = g->ndim == 2 && tile_k > 0 && ncells <= tile_cells && !timed;
+    // Four steps per sweep with the time levels in LDS (pdehip_march4.inc: one read and one write of the field per four steps) where
+    // e4plan::plan admits the grid: all-periodic fp64 3-D diffusion, by default only fields far beyond the Infinity Cache.  PDEHIP_EULER4=0 /
+    // =1: off / on at any size (read at every call).  A run of N steps is N / 4 such sweeps, then the two-step and one-step tail.
+    bool four_ok = rhs->kind == PDEHIP_RHS_DIFFUSION && g->ndim == 3;
     auto advance = [&](void *c, void *n, void *st, int64_t left, int *took, int64_t step = 0) -> int {
         if (two_arr && left >= 2) {
             if (timed) PDEHIP_TRY(bcprog_run_pair(rhs->bc_program, rhs->t + (double)step * dt, rhs->t + (double)(step + 1) * dt, st));
@@ -221,6 +227,12 @@ int pdehip_euler_run(const pdehip_grid_t *g, const pdehip_rhs_t *rhs, void *buf_
             PDEHIP_TRY(euler_multi_2d(g, rhs, c, n, dt, k, st, &done));
             if (done) { *took = k; return 0; }
             tile_ok = false;
+        }
+        if (four_ok && left >= 4) {
+            bool done = false;
+            PDEHIP_TRY(euler4_with_input_bcs(g, c, n, rhs->param, dt, rhs->bc_c, !timed && !array_faces, st, &done));
+            if (done) { *took = 4; return 0; }
+            four_ok = false;
         }
         if (two_ok && left >= 2) {
             bool done = false;
@@ -243,6 +255,7 @@ int pdehip_euler_run(const pdehip_grid_t *g, const pdehip_rhs_t *rhs, void *buf_
         GraphKey key;
         memset(&key, 0, sizeof(key));
         key.g = *g; key.rhs = *rhs; key.rhs.t = 0; key.buf[0] = buf_a; key.buf[1] = buf_b; key.dt = dt; key.kind = 0;
+        key.euler4 = e4plan::knob_from_env();
         PDEHIP_TRY(replay_graph(key, nsteps, kGraphSteps, 2048, stream, [&](void *cap) -> int {
             for (int64_t q = 0; q < kGraphSteps;) {
                 int took = 0;
