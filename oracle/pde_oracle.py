@@ -247,6 +247,20 @@ def max_abs_diff(g, ncomp, a_full, b_full):
     return err.value
 
 
+def integrate(g, ncomp, arr_full, cell_volume):
+    """Integral of each component over the grid: the sequential sum of the numba loop (pde/backends/numba/backend.py:600-606)."""
+    out = np.zeros(ncomp, dtype=np.float64)
+    _check(lib().oracle_integrate(C.byref(g), ncomp, _p(arr_full), float(cell_volume), _p(out)), "integrate")
+    return out
+
+
+def count_nonfinite(g, ncomp, arr_full):
+    """Number of NaN / +-inf cells of each component (ConsistencyTracker, pde/trackers/trackers.py:974-1003)."""
+    out = np.zeros(ncomp, dtype=np.float64)
+    _check(lib().oracle_count_nonfinite(C.byref(g), ncomp, _p(arr_full), _p(out)), "count_nonfinite")
+    return out
+
+
 def make_rhs(kind, param, bc_c, bc_mu=None, scratch_mu: np.ndarray | None = None) -> _abi.RHS:
     r = _abi.RHS()
     r.kind = kind

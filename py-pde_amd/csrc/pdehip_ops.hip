@@ -3,6 +3,9 @@
 // over the interior rows of the aligned device layout).
 #include "pdehip_common.h"
 
+#include <map>
+#include <mutex>
+
 namespace pdehip {
 
 struct DevGrid {
@@ -215,6 +218,26 @@ __global__ void __launch_bounds__(256) final_sum_kernel(SumArgs a)
     for (int q = threadIdx.x; q < a.nblocks; q += blockDim.x) acc += a.partial[(long)a.comp * a.nblocks + q];
     const double s = block_sum(acc);
     if (threadIdx.x == 0) a.out[a.comp] = s;
+}
+
+// The partial sums of the two passes: 64 components x 1024 workgroups, one buffer per STREAM, allocated at the stream's first
+// reduction and kept for the process.  Calls on one stream are ordered, so pdehip_integrate and pdehip_count_nonfinite share the
+// buffer; two streams reducing at the same time must not (one process-wide buffer let the second pass of one call read the first
+// pass of the other: tests/test_hip_pointwise.py::test_integrate_two_streams).
+constexpr int kSumBlocks = 1024;
+static int sum_scratch(hipStream_t st, double **partial)
+{
+    static std::mutex mu;
+    static std::map<hipStream_t, double *> table;
+    std::lock_guard<std::mutex> lock(mu);
+    auto it = table.find(st);
+    if (it == table.end()) {
+        double *p = nullptr;
+        PDEHIP_HIP(hipMalloc(&p, sizeof(double) * 64 * kSumBlocks));
+        it = table.emplace(st, p).first;
+    }
+    *partial = it->second;
+    return 0;
 }
 
 // ---- Gaussian white noise increment of an Euler-Maruyama step (pde/solvers/euler.py:66-147) -----------------------------
@@ -995,14 +1018,14 @@ int pdehip_integrate(const pdehip_grid_t *g, int ncomp, const void *arr_full, do
     PDEHIP_TRY(norm_grid(g, &n));
     if (!arr_full || !out_dev) PDEHIP_FAIL(E_VALUE, "integrate: NULL pointer");
     if (ncomp < 1 || ncomp > 64) PDEHIP_FAIL(E_VALUE, "integrate: 1..64 components");
-    static double *partial = nullptr;   // 64 components x 1024 workgroups, allocated once per process
-    constexpr int kBlocks = 1024;
-    if (!partial) PDEHIP_HIP(hipMalloc(&partial, sizeof(double) * 64 * kBlocks));
+    constexpr int kBlocks = kSumBlocks;
+    hipStream_t st = as_stream(stream);
+    double *partial = nullptr;
+    PDEHIP_TRY(sum_scratch(st, &partial));
     SumArgs a;
     a.g = dev_grid(n); a.in = arr_full; a.partial = partial; a.out = out_dev; a.vol = cell_volume;
     long blocks = (n.n[0] * n.n[1] * n.n[2] + 255) / 256;
     a.nblocks = (int)(blocks < kBlocks ? (blocks < 1 ? 1 : blocks) : kBlocks);
-    hipStream_t st = as_stream(stream);
     for (int c = 0; c < ncomp; c++) {
         a.comp = c;
         if (n.dtype == PDEHIP_F64) hipLaunchKernelGGL((partial_sum_kernel<double>), dim3(a.nblocks), dim3(256), 0, st, a);
@@ -1019,14 +1042,14 @@ int pdehip_count_nonfinite(const pdehip_grid_t *g, int ncomp, const void *arr_fu
     PDEHIP_TRY(norm_grid(g, &n));
     if (!arr_full || !out_dev) PDEHIP_FAIL(E_VALUE, "count_nonfinite: NULL pointer");
     if (ncomp < 1 || ncomp > 64) PDEHIP_FAIL(E_VALUE, "count_nonfinite: 1..64 components");
-    static double *partial = nullptr;
-    constexpr int kBlocks = 1024;
-    if (!partial) PDEHIP_HIP(hipMalloc(&partial, sizeof(double) * 64 * kBlocks));
+    constexpr int kBlocks = kSumBlocks;
+    hipStream_t st = as_stream(stream);
+    double *partial = nullptr;
+    PDEHIP_TRY(sum_scratch(st, &partial));
     SumArgs a;
     a.g = dev_grid(n); a.in = arr_full; a.partial = partial; a.out = out_dev; a.vol = 1.0;
     long blocks = (n.n[0] * n.n[1] * n.n[2] + 255) / 256;
     a.nblocks = (int)(blocks < kBlocks ? (blocks < 1 ? 1 : blocks) : kBlocks);
-    hipStream_t st = as_stream(stream);
     for (int c = 0; c < ncomp; c++) {
         a.comp = c;
         if (n.dtype == PDEHIP_F64) hipLaunchKernelGGL((partial_nonfinite_kernel<double>), dim3(a.nblocks), dim3(256), 0, st, a);
