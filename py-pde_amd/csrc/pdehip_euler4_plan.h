@@ -11,14 +11,41 @@ namespace e4plan {
 
 // The tile.  A workgroup owns TY x TZ outputs (rows x fastest axis) and reads (TY + 8) x (TZ + 8) cells of every input plane; a thread owns
 // a patch of PY rows x 2 cells at every level.  Work of the four levels on the shrinking regions: (38*70 + 36*68 + 34*66 + 32*64) / (4 * 32*64)
-// = 1.15 x.  (40 / PY) * (72 / 2) = 720 patches: 768 threads, the last 48 repeat patch 0 (a halo patch: it stores nothing).
+// = 1.15 x.  (40 / PY) * (72 / 2) = 720 patches: 768 threads, the last 48 repeat halo patches (patch_of_thread).
 constexpr int TY = 32, TZ = 64, PY = 2, LEVELS = 4, HALO = 4;
 constexpr int RY = TY + 2 * HALO, RZ = TZ + 2 * HALO;           // the region of level 0
 constexpr int NPY = RY / PY, NPZ = RZ / 2, PATCHES = NPY * NPZ;
 constexpr int THREADS = (PATCHES + 63) / 64 * 64;
-// one plane of one level in LDS: a ring of one row / two cells that nothing writes around the region (16-byte alignment of the patches)
+// the LDS allocation: LEVELS * LROWS * LPITCH doubles (what a row-major picture of each level with a ring around it took; the size is kept)
 constexpr int LROWS = RY + 2, LPITCH = RZ + 4;
 constexpr long LDS_BYTES = (long)LEVELS * LROWS * LPITCH * 8;
+// The image inside that allocation: one array of ARR doubles per level, patch row and patch cell, indexed by the patch number, so that a
+// wave's 64 lanes touch 64 consecutive doubles in every access; GUARD doubles in front of the first and behind the last array.
+constexpr int ARR = PATCHES, NARR = LEVELS * PY * 2, GUARD = NPZ;
+constexpr int IMAGE = GUARD + NARR * ARR + GUARD;
+static_assert(PY == 2 && IMAGE <= LEVELS * LROWS * LPITCH, "the image of the four-step sweep fits its LDS allocation");
+
+// The patch of a thread.  The THREADS - PATCHES threads behind the last patch repeat the patch 64 lower - a halo patch, it stores nothing to the
+// field: the same value twice to the same cell of the image, and in every access the lanes of the last wave still touch 64 different
+// consecutive doubles modulo 64 (repeating ONE patch would put a second address on its banks).
+constexpr int patch_of_thread(int t) { return t < PATCHES ? t : t - 64; }
+static_assert(PATCHES >= 64 && (PATCHES - 64) / NPZ * PY >= HALO + TY, "repeated patches are halo patches");
+
+// index (in doubles) of cell `cell` (0, 1) of row `row` (0 ... PY - 1) of patch `patch` at level `level` (0 ... LEVELS - 1)
+constexpr int image_index(int level, int row, int cell, int patch) { return GUARD + ((level * PY + row) * 2 + cell) * ARR + patch; }
+
+// The eight cells of a level that a patch reads from the image - the others are its own registers - as constant offsets of its own number:
+// the row above is the last row of the patch NPZ lower, the row below the first row of the patch NPZ higher, the left neighbour cell 1 of
+// the patch before, the right neighbour cell 0 of the patch behind.  At the rim of the region such an index lies in the neighbouring array
+// or in a guard run; pdehip_march4.inc says why that is harmless and tests/test_euler4_image.py enumerates it.
+enum ReadKind { RD_ABOVE0, RD_ABOVE1, RD_BELOW0, RD_BELOW1, RD_LEFT0, RD_LEFT1, RD_RIGHT0, RD_RIGHT1, READ_KINDS };
+constexpr int read_index(int level, int kind, int patch)
+{
+    return kind < RD_BELOW0  ? image_index(level, PY - 1, kind - RD_ABOVE0, patch - NPZ)
+         : kind < RD_LEFT0   ? image_index(level, 0, kind - RD_BELOW0, patch + NPZ)
+         : kind < RD_RIGHT0  ? image_index(level, kind - RD_LEFT0, 1, patch - 1)
+                             : image_index(level, kind - RD_RIGHT0, 0, patch + 1);
+}
 constexpr long MIN_CHUNK = 8;       // the fewest output planes of an x-chunk (each chunk recomputes 2 * HALO planes more)
 constexpr long WANT_CHUNK = 16;     // chunks are not made shorter than this to fill the chip
 constexpr long CUS = 256;           // one workgroup per CU (LDS)

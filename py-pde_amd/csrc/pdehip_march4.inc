@@ -8,13 +8,29 @@
 // workgroups read the same input lines (from L2).  Periodic wraps are resolved in the load addresses: rows and columns once, planes per phase.
 //
 // A thread owns the same patch of PY rows x 2 cells at every level and keeps, for each of the levels 0 ... 3, its own cells of three
-// consecutive planes in registers.  Neighbours inside the patch come from those registers; the others from the LDS copy of the level's middle
+// consecutive planes in registers.  Neighbours inside the patch come from those registers; the others from the LDS image of the level's middle
 // plane.  The levels run skewed: iteration i (local planes count from the first loaded one) computes
 //     level 1 at plane i + 1,   level 2 at plane i,   level 3 at plane i - 1,   level 4 at plane i - 2   (stored from i = 6 on)
-// between two barriers: every thread first writes the middle plane of its four register levels to LDS.  The loop is unrolled three times so
-// that the rotation of the plane buffers is a renaming (like euler2_body).  Every thread executes every barrier: halo patches skip stores,
-// nothing else, and the trip count depends on the workgroup alone.  What the first iterations compute from planes that do not exist yet
-// (zeros) never reaches a stored cell: level L at plane p reads level L - 1 at p - 1 ... p + 1 only.
+// The loop is unrolled three times so that the rotation of the plane buffers is a renaming (like euler2_body).  What the first iterations
+// compute from planes that do not exist yet (zeros) never reaches a stored cell: level L at plane p reads level L - 1 at p - 1 ... p + 1 only.
+//
+// The image (e4plan::image_index): per level, patch row and patch cell one array indexed by the patch number, sixteen arrays of 720 doubles
+// between two guard runs of 36, inside the allocation of LEVELS * LROWS * LPITCH doubles.  Every neighbour is a constant offset of the
+// thread's own index (e4plan::read_index): above [row 1][cell][patch - 36], below [row 0][cell][patch + 36], left [row][cell 1][patch - 1],
+// right [row][cell 0][patch + 1].  A wave reads or writes 64 consecutive doubles per access: no bank conflicts, whatever the base
+// (tests/test_euler4_image.py computes the banks).  What a patch at the rim of the region reads - through the row wrap (patch - 1 of a
+// row's first patch is the last one of the row above), from a neighbouring array or a guard run - is unspecified.  Such a value only ever
+// feeds a cell outside the valid region of its level: level L is valid on the region of level 0 shrunk by L cells per side,
+//     level 0: 40 x 72,   level 1: 38 x 70,   level 2: 36 x 68,   level 3: 34 x 66,   level 4: 32 x 64 (the outputs),
+// a cell that is valid at level L has all four in-plane neighbours inside the region of level L - 1, and those are read where their owners
+// stored them (the same test enumerates it).  The guard runs are zeroed once so that whole images compare equal; no result depends on it.
+//
+// A phase (one iteration) has one barrier per level: the arithmetic of level l, which reads the image of level l; a barrier - every wave
+// has read that image; then the thread stores its cells of the plane that is the middle plane of level l at the NEXT iteration (level 0:
+// plane i + 2, loaded earlier; level l: what level l - 1 has just computed).  Nothing waits for these stores but the next barrier, so they
+// are under way while the other waves of the SIMD compute; between a store and the read of the same image at the next iteration lie three
+// barriers.  Every thread executes every barrier: halo patches skip the stores to the field, nothing else, and the trip count depends on
+// the workgroup alone.
 //
 // Per cell the arithmetic is `laplace` + `update` of pdehip_march2.inc (cartesian.py:220-227) in the same order: bit-identical to four single
 // steps in the exact build.
@@ -24,11 +40,10 @@ __global__ void __launch_bounds__(e4plan::THREADS) euler4_kernel(const LapArgs a
     static_assert(sizeof(T) == 8 && (M2 == E2_DIFFUSION || M2 == E2_DIFFUSION_UNIT), "fp64 diffusion only");
     using namespace e4plan;
     typedef typename VecT<T, 2>::type V;
-    constexpr int LP = LPITCH, PLANE = LROWS * LPITCH;
-    __shared__ __attribute__((aligned(16))) T lds[LEVELS * PLANE];
+    __shared__ __attribute__((aligned(16))) T lds[LEVELS * LROWS * LPITCH];
 
-    // the threads behind the last patch repeat patch 0: a halo patch (the same values written twice, nothing stored)
-    const int tid = (int)threadIdx.x < PATCHES ? (int)threadIdx.x : 0;
+    // the threads behind the last patch repeat a halo patch (the same values written twice, nothing stored)
+    const int tid = patch_of_thread((int)threadIdx.x);
     const int py = tid / NPZ, pz = tid - py * NPZ;
     const int ly = py * PY, lz = 2 * pz;                       // first row / column of the patch in the region of level 0
     const bool owner = ly >= HALO && ly < HALO + TY && lz >= HALO && lz < HALO + TZ;   // (HALO % PY == 0: a patch is output or halo as a whole)
@@ -55,7 +70,12 @@ __global__ void __launch_bounds__(e4plan::THREADS) euler4_kernel(const LapArgs a
         for (int r = 0; r < PY; r++) dst[r] = PDEHIP_LDV((const V *)(in + po + roff[r]));
     };
 
-    const int lbase = (ly + 1) * LP + lz + 2;   // the patch's first cell in an LDS plane
+    // The patch number twice.  Every array is read twice per level, at offsets a constant apart; through the same index the compiler merges
+    // the two into one two-address read, which runs at half the rate of two single 8-byte reads.  It cannot see through the empty asm.
+    const int me = tid;
+    int me2 = tid;
+    asm volatile("" : "+v"(me2));
+    if ((int)threadIdx.x < GUARD) lds[threadIdx.x] = lds[IMAGE - GUARD + threadIdx.x] = 0;   // (no result depends on it)
 
     auto update = [&](double xm, double xp, double up, double dn, double left, double right, double cen) {
         const double vm = 2 * cen;
@@ -68,16 +88,30 @@ __global__ void __launch_bounds__(e4plan::THREADS) euler4_kernel(const LapArgs a
         const double ez = (left - vm + right) * a.sz;
         return epilogue<LAP_EULER>(ex + ey + ez, cen, cen, a.s1, a.s2, a.gamma);
     };
-    // one level up: the plane of `mid` at the next level, from the thread's cells of three planes and the LDS copy of the middle one
-    auto level = [&](const V (&old)[PY], const V (&mid)[PY], const V (&nw)[PY], const T *lp, V (&res)[PY]) {
-        const T *p = lp + lbase;
-        const V above = *(const V *)(p - LP), below = *(const V *)(p + PY * LP);
+    // the eight neighbour cells of the patch in the image of level l
+    auto fetch = [&](int l, T (&nb)[READ_KINDS]) {
+#pragma unroll
+        for (int k = 0; k < READ_KINDS; k++) {
+            const bool second = k == RD_BELOW1 || k == RD_LEFT1 || k == RD_RIGHT0 || k == RD_RIGHT1;   // the second read of its array
+            nb[k] = lds[read_index(l, k, second ? me2 : me)];
+        }
+    };
+    // one level up: the plane of `mid` at the next level, from the thread's cells of three planes and the neighbours of the middle one
+    auto level = [&](const V (&old)[PY], const V (&mid)[PY], const V (&nw)[PY], const T (&nb)[READ_KINDS], V (&res)[PY]) {
+        const V above = V{nb[RD_ABOVE0], nb[RD_ABOVE1]}, below = V{nb[RD_BELOW0], nb[RD_BELOW1]};
 #pragma unroll
         for (int r = 0; r < PY; r++) {
-            const double left = p[r * LP - 1], right = p[r * LP + 2];
+            const double left = nb[RD_LEFT0 + r], right = nb[RD_RIGHT0 + r];
             const V up = r == 0 ? above : mid[r > 0 ? r - 1 : 0], dn = r == PY - 1 ? below : mid[r < PY - 1 ? r + 1 : r];
             res[r][0] = update(old[r][0], nw[r][0], up[0], dn[0], left, mid[r][1], mid[r][0]);
             res[r][1] = update(old[r][1], nw[r][1], up[1], dn[1], mid[r][0], right, mid[r][1]);
+        }
+    };
+    auto store_level = [&](int l, const V (&pl)[PY]) {
+#pragma unroll
+        for (int r = 0; r < PY; r++) {
+            lds[image_index(l, r, 0, me)] = pl[r][0];
+            lds[image_index(l, r, 1, me)] = pl[r][1];
         }
     };
 
@@ -92,29 +126,27 @@ __global__ void __launch_bounds__(e4plan::THREADS) euler4_kernel(const LapArgs a
     load_plane(0, R[0][0]);
     load_plane(1, R[0][1]);
     load_plane(2, R[0][2]);
+#pragma unroll
+    for (int l = 0; l < LEVELS; l++) store_level(l, R[l][(4 - l) % 3]);   // the middle planes of iteration 0 (level 0: plane 1; the others: zeros)
+    __syncthreads();
 
     // iteration i, i mod 3 == K: level 0 holds planes i, i + 1, i + 2 in slots K, K + 1, K + 2 (mod 3); level L the planes L lower
     auto phase = [&](int i, auto kc) {
         constexpr int K = decltype(kc)::value;
         load_plane(i + 3, pre);   // needed at the next iteration
 #pragma unroll
-        for (int l = 0; l < LEVELS; l++) {   // the middle planes: level 0 plane i + 1, level 1 plane i, ...
-            const V (&mid)[PY] = R[l][(K + 4 - l) % 3];
-#pragma unroll
-            for (int r = 0; r < PY; r++) *(V *)(lds + l * PLANE + lbase + r * LP) = mid[r];
-        }
-        __syncthreads();
-#pragma unroll
         for (int l = 0; l < LEVELS; l++) {
             // level l holds planes (i - l, i + 1 - l, i + 2 - l); level l + 1 gets plane i + 1 - l, in the slot of its plane i - 2 - l
             const V (&old)[PY] = R[l][(K + 3 - l) % 3];
             const V (&mid)[PY] = R[l][(K + 4 - l) % 3];
             const V (&nw)[PY] = R[l][(K + 5 - l) % 3];
+            T nb[READ_KINDS];
+            fetch(l, nb);
             if (l < LEVELS - 1) {
-                level(old, mid, nw, lds + l * PLANE, R[l + 1][(K + 4 - l) % 3]);
+                level(old, mid, nw, nb, R[l + 1][(K + 4 - l) % 3]);
             } else {
                 V res[PY];
-                level(old, mid, nw, lds + l * PLANE, res);
+                level(old, mid, nw, nb, res);
                 const int q = i - 2;   // the local plane of level 4: output plane x0 + q - HALO
                 if (owner && q >= HALO) {
                     const long po = (x0 + q - HALO) * a.p0;
@@ -122,8 +154,9 @@ __global__ void __launch_bounds__(e4plan::THREADS) euler4_kernel(const LapArgs a
                     for (int r = 0; r < PY; r++) __builtin_nontemporal_store(res[r], (V *)(out + po + roff[r]));
                 }
             }
+            __syncthreads();        // every wave has read the image of level l: the middle plane of the next iteration takes its place
+            store_level(l, nw);
         }
-        __syncthreads();
 #pragma unroll
         for (int r = 0; r < PY; r++) R[0][K][r] = pre[r];   // plane i is dead: plane i + 3 takes its slot
     };
