@@ -23,12 +23,17 @@
  *     are aligned dwordx4).  pdehip_layout() reports pitches and the allocation size;
  *     pdehip_valid_to_full / pdehip_hostfull_to_full convert from the host layouts.  Layers
  *     along axis 0 stay contiguous (one block per slab face for the halo exchange).
- *   - dtype PDEHIP_F32 stores fp32 but all arithmetic between a load and the store
- *     of one kernel runs in fp64 registers (numba promotes float32 array elements
- *     against float64 closure constants the same way, SURVEY.md §7 "fp32").
+ *   - dtype PDEHIP_F32 stores fp32.  TWO arithmetic modes exist for such fields, chosen PER CALL by the entry point:
+ *       "fp64" (default; every entry point but the three below): all arithmetic between a load and the store of
+ *         one kernel runs in fp64 registers (numba promotes float32 array elements against float64 closure
+ *         constants the same way, SURVEY.md §7 "fp32"), rounded to fp32 once at the store;
+ *       "fp32" (pdehip_laplace_f32p, pdehip_euler_run_f32p; pdehip_f32p_supported is their dry run): every operation
+ *         is rounded to fp32 and the constants dx**-2, D and dt enter as fp32 - the arithmetic of the reference's
+ *         torch backend on fp32 fields, bit for bit (contract at those entry points).
  *   - the arithmetic of every kernel follows the reference expression order and is
  *     compiled with -ffp-contract=off, so results are bit-identical to the CPU
- *     oracle (oracle/pde_oracle.c) and to the reference's eager torch-CPU backend.
+ *     oracle (oracle/pde_oracle.c) and to the reference's eager torch-CPU backend
+ *     (fp32 fields: the default mode matches the reference's numba backend, the "fp32" mode its torch backend).
  */
 #ifndef PDEHIP_H
 #define PDEHIP_H
@@ -88,9 +93,11 @@ enum {
     PDEHIP_RHS_DIFFUSION = 0,    /* D * laplace(c)            pde/pdes/diffusion.py:119-121 */
     PDEHIP_RHS_CAHN_HILLIARD = 1 /* laplace(c**3 - c - g*laplace(c)) pde/pdes/cahn_hilliard.py:115-122 */
 };
+/* flags in pdehip_rhs_t.reserved, read ONLY by the entry points that say so (0 everywhere else) */
+enum { PDEHIP_RHS_F32P_ONE_STEP = 1 /* pdehip_euler_run_f32p: one step per launch on every grid (the instance the two-step sweep is tested against) */ };
 typedef struct pdehip_rhs {
     int32_t kind;
-    int32_t reserved;
+    int32_t reserved;               /* PDEHIP_RHS_* flags, else 0 */
     double param;                   /* diffusivity D, or interface_width g */
     pdehip_bc_face_t bc_c[2 * PDEHIP_MAX_DIM];  /* BCs of the state field */
     pdehip_bc_face_t bc_mu[2 * PDEHIP_MAX_DIM]; /* BCs of mu (Cahn-Hilliard only) */
@@ -822,6 +829,46 @@ int pdehip_interpolate_to_grid(const pdehip_grid_t *src, int ncomp, const int *p
  * twelve edges the same way from the two adjacent face ghost cells, then corner = (sum of the three adjacent edge cells) / 3; in the
  * field's own type, like numpy.  1-D grids: nothing to do.  pdehip_set_ghost_cells itself is unchanged. */
 int pdehip_set_ghost_corners(const pdehip_grid_t *g, int ncomp, void *data_full, void *stream);
+
+/* ---- the PURE-fp32 arithmetic mode of fp32 fields (optional entry points; the ABI version stays 8) --------------------------------
+ * Write (-), (+), (x) for fp32 operations, each rounded to fp32, never contracted (-ffp-contract=off), and s_a = fp32(dx_a ** -2) (the
+ * power in double, rounded once).  The contract:
+ *     per-axis term    t_a = ((l_a (-) 2c) (+) r_a) (x) s_a            (2c is exact)
+ *     Laplacian        t_0,  t_0 (+) t_1,  (t_0 (+) t_1) (+) t_2        in grid-axis order
+ *     Euler step       u' = u (+) (fp32(dt) (x) (fp32(D) (x) lap(u)))
+ *     a zero-derivative face: the neighbour beyond the wall IS the adjacent cell (a copy, no arithmetic); a periodic face: the cell at
+ *     the other end of the axis
+ *     k steps in one sweep equal k single steps bit for bit (the intermediate level is an fp32 value either way).
+ * This is the arithmetic of the reference's torch backend on fp32 fields: the Laplacian of pde/backends/torch/operators/cartesian.py:55-83
+ * and the Euler update of pde/backends/torch/_solvers.py:149 (`state + dt * rhs`, DiffusionPDE's `D * laplace(state)`,
+ * pde/pdes/diffusion.py:119-121).  A numpy fp32 restatement of the lines above equals that backend bit for bit for the Laplacian with
+ * value / derivative / mixed faces (ghost cells from `set_ghost_cells` on the fp32 field) and for Euler runs with periodic and
+ * zero-derivative faces (tests/golden/make_golden_f32p.py asserts it).  It does NOT hold for inhomogeneous faces inside the Euler loop:
+ * the reference's torch stepper rounds their ghost cells differently from its own `set_ghost_cells` - the loop refuses them.
+ *
+ * The mode travels per call, by the choice of entry point; there is no process-wide switch.  fp32 grids only (PDEHIP_E_NOTIMPL else).
+ *
+ * pdehip_laplace_f32p: pdehip_laplace in this arithmetic (same arguments; the caller has set the ghost cells of in_full).  Replaces the
+ * closure of make_laplace of the torch backend (pde/backends/torch/operators/cartesian.py:55-83).  3-D grids whose fastest axis is a
+ * multiple of four cells: lap32_kernel<march> (register march along axis 0, 16-byte row accesses, fastest-axis neighbours by DPP);
+ * everything else: lap32_kernel<generic> (one cell per thread). */
+int pdehip_laplace_f32p(const pdehip_grid_t *g, const void *in_full, void *out, int out_layout, void *stream);
+/* pdehip_euler_run_f32p: pdehip_euler_run for PDEHIP_RHS_DIFFUSION in this arithmetic: `nsteps` explicit Euler steps, ping-ponging
+ * between buf_a (initial state) and buf_b; *result receives the buffer holding the final state.  Replaces the fixed-step loop of the
+ * torch backend (EulerStepper, pde/backends/torch/_solvers.py:127-149) for DiffusionPDE.  Every axis must be periodic or zero-derivative
+ * on both sides (scalar first-order faces with const 0, factor 1 and the periodic / adjacent index; PDEHIP_E_NOTIMPL otherwise, before
+ * anything is launched); ghost cells of the buffers are neither read nor written.  3-D grids whose fastest axis is a multiple of four
+ * cells and at most 1024 (two cells at least on the other axes): euler32_kernel<two-step> advances two steps per sweep, an odd last step and every other grid take
+ * euler32_kernel<generic> (one step per launch, any number of axes, any extent; rhs->reserved & PDEHIP_RHS_F32P_ONE_STEP forces it for that call:
+ * the yardstick the two-step instance is tested against). */
+int pdehip_euler_run_f32p(const pdehip_grid_t *g, const pdehip_rhs_t *rhs, void *buf_a, void *buf_b, double dt, int64_t nsteps,
+                          void **result, void *stream);
+/* Dry run: *answer = 0 when pdehip_laplace_f32p (rhs == NULL) / pdehip_euler_run_f32p (rhs given) would refuse the grid or the faces,
+ * 1 = accepted by the one-cell-per-thread instance, 2 = accepted by the march / two-step instance.  The answer is about grid and faces
+ * only: the march / two-step instances also need every array on a 16-byte boundary (what pdehip_malloc and the component pitches of
+ * pdehip_layout give) and a call without PDEHIP_RHS_F32P_ONE_STEP - a call that fails either takes the one-cell-per-thread instance,
+ * with equal bits (pdehip_last_kernel_name tells).  Launches nothing; always returns 0 (pdehip_last_error holds the reason of a refusal). */
+int pdehip_f32p_supported(const pdehip_grid_t *g, const pdehip_rhs_t *rhs, int *answer);
 
 #ifdef __cplusplus
 }

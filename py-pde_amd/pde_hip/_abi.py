@@ -20,6 +20,7 @@ OUT_VALID, OUT_FULL = 0, 1
 BC_SKIP, BC_ORDER1, BC_ORDER2 = 0, 1, 2
 BCF_ARRAYS, BCF_NORMAL = 1, 2
 RHS_DIFFUSION, RHS_CAHN_HILLIARD = 0, 1
+RHS_F32P_ONE_STEP = 1   # flag in RHS.reserved, read by pdehip_euler_run_f32p only
 
 METHODS = {"central": CENTRAL, "forward": FORWARD, "backward": BACKWARD}
 
@@ -360,6 +361,10 @@ OPTIONAL_PROTOTYPES: dict[str, list] = {
     "interpolate_points": [_pg, _i, C.POINTER(_i), _pd, _i, _vp, _vp, _i64, _vp, _vp, _vp, _vp],
     "interpolate_to_grid": [_pg, _i, C.POINTER(_i), _pd, _i, _vp, _pg, _vp, _vp, _vp, _vp, _vp, _vp],
     "set_ghost_corners": [_pg, _i, _vp, _vp],
+    # the pure-fp32 arithmetic mode of fp32 fields: Laplacian, diffusion Euler loop, dry run (csrc/pdehip_f32p.hip)
+    "laplace_f32p": [_pg, _vp, _vp, _i, _vp],
+    "euler_run_f32p": [_pg, _pr, _vp, _vp, _d, _i64, _pvp, _vp],
+    "f32p_supported": [_pg, _pr, C.POINTER(_i)],
 }
 
 

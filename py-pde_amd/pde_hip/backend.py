@@ -75,6 +75,7 @@ class HipBackendMixin(OperatorGlueMixin, InterpolationMixin, RhsPlanningMixin, N
         without a GPU.  The first compute call selects the device and raises ``RuntimeError`` without one."""
         self._device_request = None if device is None else int(device)
         self._fastmath: bool | None = None   # None: from the configuration / PDEHIP_FASTMATH (see `fastmath`)
+        self._f32_arithmetic: str | None = None   # None: from the configuration / PDEHIP_F32_ARITHMETIC (see `f32_arithmetic`)
         self.stream = None  # HIP default stream; multi-GPU paths create their own
         self._info_cache: dict[tuple, GridInfo] = {}
 
@@ -100,6 +101,34 @@ class HipBackendMixin(OperatorGlueMixin, InterpolationMixin, RhsPlanningMixin, N
 
         if current_device() is not None:
             _ = self._lib      # a device is selected already: the mode reaches the library now (operators made earlier hold the library, not this property)
+
+    @property
+    def f32_arithmetic(self) -> str:
+        """Arithmetic of the stencil kernels on fp32 fields: ``"fp64"`` (default) = fp64 registers between load and store, like the
+        reference's numba backend; ``"fp32"`` = every operation rounded to fp32, bit for bit the reference's torch backend
+        (``pde/backends/torch/operators/cartesian.py:55-83``, ``pde/backends/torch/_solvers.py:149``; contract in ``include/pdehip.h``).
+        Order: ``backend.f32_arithmetic = "fp32"`` on the object; else the configuration - ``config["backend.hip.f32_arithmetic"]``
+        with py-pde, whose plugin ALWAYS holds a value (default ``"fp64"``), so the environment is not consulted there; else (the
+        stand-alone backend without a configuration entry) ``PDEHIP_F32_ARITHMETIC=fp32``.  An operator or a stepper captures the mode when it is MADE; the mode travels per call (the choice of entry
+        point), the library keeps no state.  ``"fp32"`` serves the 3 / 5 / 7-point Laplacian and the fixed-step Euler loop of
+        ``DiffusionPDE`` with periodic / zero-derivative axes; every other stencil computation on an fp32 field raises
+        ``NotImplementedError`` in that mode (pde_hip/f32p.py).  fp64 fields are not affected."""
+        from .f32p import check_mode
+
+        if self._f32_arithmetic is not None:
+            return self._f32_arithmetic
+        try:
+            if "f32_arithmetic" in self.config:
+                return check_mode(self.config["f32_arithmetic"])
+        except TypeError:
+            pass
+        return check_mode(os.environ.get("PDEHIP_F32_ARITHMETIC", "fp64"))
+
+    @f32_arithmetic.setter
+    def f32_arithmetic(self, value) -> None:
+        from .f32p import check_mode
+
+        self._f32_arithmetic = None if value is None else check_mode(value)
 
     @property
     def _lib(self):

@@ -8,7 +8,9 @@ the device full layout and ``arr_full`` must have valid ghost cells.
 
 from __future__ import annotations
 
-from . import _abi
+import numpy as np
+
+from . import _abi, f32p
 from .device import DeviceArray
 
 
@@ -76,10 +78,19 @@ def make_laplace(grid, *, backend, corner_weight: float | None = None, spectral:
         laplace9.grid = grid
         return laplace9
 
+    f32_mode = backend.f32_arithmetic      # captured now: "fp32" sends fp32 arrays to pdehip_laplace_f32p (pde_hip/f32p.py)
+    f32_missing = f32_mode == "fp32" and not lib.has(*f32p.ENTRY_POINTS)    # checked once, here
+
     def laplace(arr: DeviceArray, out: DeviceArray) -> None:
+        if f32_mode == "fp32" and arr.dtype == np.float32:
+            if f32_missing:
+                f32p.require_entry_points(lib)      # raises, naming the symbols
+            f32p.laplace(backend, lib, arr, out)
+            return
         lib.laplace(arr.info.ref, arr.ptr, out.ptr, _abi.OUT_FULL, backend.stream)
 
     laplace.grid = grid
+    laplace._f32p_ok = True
     return laplace
 
 

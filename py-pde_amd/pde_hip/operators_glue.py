@@ -135,7 +135,15 @@ class OperatorGlueMixin:
         """``impl(arr_full: DeviceArray, out: DeviceArray)``; ghost cells are the caller's job."""
         info = self.get_operator_info(grid, operator)
         kwargs.pop("bcs", None)      # (operators made of their conditions say themselves that they need `make_operator`)
-        return info.factory(grid, backend=self, **kwargs)
+        op = info.factory(grid, backend=self, **kwargs)
+        if self.f32_arithmetic == "fp32":
+            # the pure-fp32 mode, captured now: an operator without a pure-fp32 kernel refuses fp32 arrays (pde_hip/f32p.py)
+            from . import f32p
+
+            message = f32p.operator_refusal(self, str(getattr(info, "name", operator)), op)
+            if message is not None:
+                op = f32p.guard_operator(op, message, lambda arr: getattr(arr, "dtype", None))
+        return op
 
     def _apply_operator(self, func, *values: np.ndarray, out: np.ndarray, grid=None, **kwargs) -> None:
         """Apply a native operator to host FULL arrays and write host ``out`` (base.py:239-254).
@@ -182,14 +190,45 @@ class OperatorGlueMixin:
         is returned.
         """
         info = self.get_operator_info(grid, operator)
+        f32_refusal = None          # the pure-fp32 mode, captured now: the message with which fp32 operands are refused (pde_hip/f32p.py)
         if getattr(info.factory, "_hip_needs_bcs", False):
             # `poisson_solver`: the conditions are part of the operator (the reference's `factory(bcs=...)`, pde/pdes/laplace.py:79)
-            return info.factory(grid, backend=self, bcs=bcs, dtype=dtype, **kwargs)
+            if self.f32_arithmetic != "fp32":
+                return info.factory(grid, backend=self, bcs=bcs, dtype=dtype, **kwargs)
+            # the pure-fp32 mode: fp32 right-hand sides are refused before the solver is built; other types get the solver on first use
+            from . import f32p
+
+            message = f32p.refusal(f"operator `{getattr(info, 'name', operator)}`")
+            built: list = []
+
+            def solve(arr, *args, **kw):
+                if f32p.is_f32(dtype if dtype is not None and not isinstance(arr, DeviceArray) else getattr(arr, "dtype", None)):
+                    raise NotImplementedError(message)
+                if not built:
+                    built.append(info.factory(grid, backend=self, bcs=bcs, dtype=dtype, **kwargs))
+                return built[0](arr, *args, **kw)
+
+            solve.grid = grid  # type: ignore[attr-defined]
+            return solve
         op_no_bc = info.factory(grid, backend=self, **kwargs)
+        if self.f32_arithmetic == "fp32":
+            from . import f32p
+
+            f32_refusal = f32p.operator_refusal(self, str(getattr(info, "name", operator)), op_no_bc)
         nd = len(grid.shape)
         shape_in = (grid.dim,) * info.rank_in + tuple(grid.shape)
         shape_out = (grid.dim,) * info.rank_out + tuple(grid.shape)
         if dtype is not None and np.dtype(dtype).kind == "c":
+            if self.f32_arithmetic == "fp32" and np.dtype(dtype) == np.dtype(np.complex64):
+                from . import f32p
+
+                message = f32p.complex_refusal(str(getattr(info, "name", operator)))
+
+                def refuse_complex64(arr, out=None, args=None):
+                    raise NotImplementedError(message)
+
+                refuse_complex64.grid = grid  # type: ignore[attr-defined]
+                return refuse_complex64
             return self._make_complex_operator(grid, operator, info, op_no_bc, bcs, dtype, shape_in, shape_out)
         set_ghosts = self.make_ghost_cell_setter(bcs)
 
@@ -202,6 +241,8 @@ class OperatorGlueMixin:
                 msg = f"Incompatible shapes {tuple(out.shape)} != {shape_out}"
                 raise ValueError(msg)
             ginfo = self.grid_info(grid, arr.dtype if dtype is None or not host else dtype)
+            if f32_refusal is not None and ginfo.dtype == np.float32:
+                raise NotImplementedError(f32_refusal)      # before anything is uploaded or launched
             native = DeviceArray(ginfo, shape_in[: len(shape_in) - nd]).set_valid(np.asarray(arr), self.stream) if host else arr
             set_ghosts(native, args=args)
             res = out if isinstance(out, DeviceArray) else DeviceArray(native.info, shape_out[: len(shape_out) - nd])

@@ -51,6 +51,14 @@ DEFAULT_CONFIG = {
         "results bit-identical to the numpy / torch-CPU backends.  True: the same kernels with FMA contraction, like the numba backend under "
         "its default `backend.numba.fastmath` - fewer fp64 operations per cell, results within 1e-10 (relative) of the exact build.",
     ),
+    "f32_arithmetic": Parameter(
+        value="fp64",
+        cls=str,
+        description="Arithmetic of the stencil kernels on float32 fields.  'fp64' (default): fp64 registers between load and store, like the "
+        "numba backend.  'fp32': every operation rounded to float32 - bit for bit the torch backend's float32 results; serves `laplace` and "
+        "the fixed-step Euler loop of DiffusionPDE with periodic / zero-derivative axes, every other stencil computation on a float32 field "
+        "raises NotImplementedError.  Captured when an operator or stepper is made.",
+    ),
     "resident_state": Parameter(
         value=True,
         cls=bool,
@@ -209,6 +217,10 @@ class HipSlabSolver(AdaptiveSolverBase):
             dt = self.dt_default
         self.info.update(dt=float(dt), steps=0, dt_adaptive=bool(self.adaptive), stochastic=False, scheme=self.scheme, post_step_data=None)
         self._select_backend(state)
+        if getattr(self.backend, "f32_arithmetic", "fp64") == "fp32" and np.dtype(state.dtype) == np.dtype(np.float32):
+            from .f32p import refusal
+
+            raise NotImplementedError(refusal(f"solver `{self.name}` (decomposed grids)", "the slab and block loops compute fp32 fields in fp64 registers"))
         # a post-step hook runs between the steps, on the host, on the box of each rank - the semantics of the reference's MPI solver
         # ("post_step_hook can only be used to do local modifications", pde/solvers/explicit_mpi.py:43-49): never inside the fused C loops
         try:

@@ -361,6 +361,10 @@ class RhsPlanningMixin:
         called without a grid, e.g. by ``ScipySolver``) is uploaded here, where the grid is known."""
         grid = state.grid
         is_complex = np.dtype(state.dtype).kind == "c"
+        if self.f32_arithmetic == "fp32" and np.dtype(state.dtype) == np.dtype(np.float32):
+            from .f32p import refusal      # the fused right-hand sides compute in fp64 registers (pde_hip/f32p.py)
+
+            raise NotImplementedError(refusal(f"the right-hand side of {type(eq).__name__} (`make_pde_rhs`)"))
         info = self.grid_info(grid, real_dtype_of(state.dtype))
         comp_shape = tuple(np.shape(state.data))[: np.ndim(state.data) - len(info.shape)]   # (n,) for a FieldCollection
         if is_complex:

@@ -546,6 +546,18 @@ class StepperMixin:
         scheme = classify_solver(solver, lambda: self._lib.has("fixedpoint_ctl_bytes", "fixedpoint_run", "jit_fixedpoint_run"))
         post_step = self._make_host_post_step(solver, state)
         add_noise = self._make_noise_step(solver, scheme, state)
+        if self.f32_arithmetic == "fp32" and np.dtype(state.dtype) == np.dtype(np.float32):
+            # the pure-fp32 arithmetic mode (pde_hip/f32p.py): the Euler loop of DiffusionPDE, or a refusal - never fp64 registers
+            from . import f32p
+
+            why = f32p.stepper_refusal(self, solver, state, scheme, add_noise is not None, post_step is not None)
+            if why is not None:
+                raise NotImplementedError(why)
+            f32p.require_entry_points(self._lib)
+            spec = self.make_rhs_spec(solver.pde, state)
+            if spec.host_time_dependent or spec.c.kind != _abi.RHS_DIFFUSION:
+                raise NotImplementedError(f32p.refusal(f"solver {scheme.name} with these boundary conditions"))
+            return f32p.make_euler_stepper(self, self._lib, spec, float(solver.info["dt"]), solver.info, _hand_back)
         if add_noise is not None:
             # Euler-Maruyama: deterministic Euler step, noise increment, then the hook (pde/solvers/euler.py:120-141)
             hook = post_step
