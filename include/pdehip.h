@@ -870,6 +870,31 @@ int pdehip_euler_run_f32p(const pdehip_grid_t *g, const pdehip_rhs_t *rhs, void 
  * with equal bits (pdehip_last_kernel_name tells).  Launches nothing; always returns 0 (pdehip_last_error holds the reason of a refusal). */
 int pdehip_f32p_supported(const pdehip_grid_t *g, const pdehip_rhs_t *rhs, int *answer);
 
+/* ---- statistics of a field where it lives (optional entry points; the ABI version stays 8) ----------------------------------------
+ * What a tracker asks of a running simulation without moving the state to the host.  Both entries read the INTERIOR cells of full
+ * arrays in the device layout (ghost cells and row padding never enter a result), sweep with 16-byte loads where the row length allows,
+ * leave one partial result per wave in a fixed slot and fold the slots with one workgroup in a fixed order: no atomics, two runs give
+ * equal bits.  The slots (1.3 MB) are kept per stream and freed by pdehip_release_scratch.
+ *
+ * pdehip_field_stats: replaces the host reductions behind `DataFieldBase.integral`, `.average`, `.fluctuations` and `.magnitude`
+ * (pde/fields/datafield_base.py:846-897; `grid.integrate` = sum x cell volume on Cartesian grids, `np.std` = numpy's two-pass variance).
+ * For every component c (1 <= ncomp <= 64) eight doubles at out_dev + 8 * c:
+ *     {n_finite, n_nonfinite, sum, min, max, mean, m2, 0}
+ * sum, min and max over the FINITE cells, in fp64 from values converted exactly; mean = sum / n_finite; m2 = sum of (x - mean)^2 over the
+ * finite cells, by a SECOND sweep on the same stream that reads the mean from out_dev (launched only with want_m2 != 0, else m2 = NaN).
+ * n_finite == 0: min, max, mean and m2 are NaN.  norm != 0: ONE block of eight for s = sqrt(x_0 * x_0 + x_1 * x_1 + ...) over the
+ * components, evaluated in the field's own type in component order, one rounding per operation: the norm behind `to_scalar("auto")` of
+ * vector and tensor fields (pde/fields/vectorial.py:420-431, pde/fields/tensorial.py:333-337). */
+int pdehip_field_stats(const pdehip_grid_t *g, int ncomp, const void *arr_full, int norm, int want_m2, double *out_dev, void *stream);
+/* pdehip_steady_state: the test of `SteadyStateTracker.handle` (pde/trackers/trackers.py:819-844) in ONE sweep over all components: for
+ * every interior cell where `cur` is finite r = |(last - cur) / elapsed| - rtol * |cur|, in the field's type and in this order (a
+ * division, not a product with a reciprocal; elapsed and rtol rounded to the field's type first, like a Python float next to an fp32
+ * array).  out_dev[0] = max r (NaN if any such r is NaN, like np.max; NaN too when no cell took part), out_dev[1] = number of cells
+ * that took part.  The same sweep copies cur to last in EVERY interior cell, the others included (`self._last_data[:] = field.data`);
+ * ghost cells of `last` are left alone.  `last_full` must not be `cur_full`. */
+int pdehip_steady_state(const pdehip_grid_t *g, int ncomp, const void *cur_full, void *last_full, double elapsed, double rtol,
+                        double *out_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

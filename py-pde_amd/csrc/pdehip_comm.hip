@@ -542,7 +542,7 @@ int pdehip_comm_destroy(void *comm)
 int pdehip_release_scratch(void)
 {
     release_scratch(serial_context());
-    return 0;
+    return stats_release_scratch();
 }
 
 // what RCCL itself says about the communicator: out5 = {ncclCommCount, ncclCommUserRank, ncclCommCuDevice, ncclGetVersion, HIP device of the

@@ -154,6 +154,7 @@ struct Euler2Plan {
     bool has_y;
 };
 int preload_shell_kernels();     // pdehip_shell.hip: the same for its code object
+int stats_release_scratch();     // pdehip_stats.hip: frees the per-stream slots of its sweeps (pdehip_release_scratch)
 #include "pdehip_launchers.h"
 namespace exactv {
 #include "pdehip_launchers.h"

@@ -70,6 +70,57 @@ __device__ __forceinline__ void sum_slots(const double *slots, int n, double (&o
 #pragma unroll
     for (int q = 0; q < N; q++) out[q] = part[q][0];
 }
+// ---- minimum / maximum: the same two halves as wave_sum (pdehip_device.h) and sum_slots.  A minimum or maximum does not depend on the
+// order, so the bits are those of any other order; the operands must not be NaN (the callers select finite values, or flag a NaN in a
+// column of its own).
+struct SlotMin {
+    __device__ static double identity() { return __longlong_as_double(0x7ff0000000000000LL); }    // +inf
+    __device__ static double apply(double a, double b) { return b < a ? b : a; }
+};
+struct SlotMax {
+    __device__ static double identity() { return __longlong_as_double((long long)0xfff0000000000000ULL); }    // -inf
+    __device__ static double apply(double a, double b) { return b > a ? b : a; }
+};
+template <class OP>
+__device__ __forceinline__ double wave_reduce(double v)
+{
+#pragma unroll
+    for (int ofs = 32; ofs >= 1; ofs >>= 1) v = OP::apply(v, __shfl_xor(v, ofs, 64));
+    return v;
+}
+__device__ __forceinline__ double wave_min(double v) { return wave_reduce<SlotMin>(v); }
+__device__ __forceinline__ double wave_max(double v) { return wave_reduce<SlotMax>(v); }
+// OP over N interleaved columns of wave results by ONE workgroup of 256 threads; every thread returns with the results
+template <class OP, int N>
+__device__ __forceinline__ void reduce_slots(const double *slots, int n, double (&out)[N])
+{
+    __shared__ double part[N][256];
+#pragma unroll
+    for (int q = 0; q < N; q++) out[q] = OP::identity();
+    // four slots per round: the loads of a round do not wait for one another (a fold of 32768 slots is 32 rounds instead of 128)
+    for (int i = threadIdx.x; i < n; i += 4 * 256) {
+        double v[4][N];
+#pragma unroll
+        for (int u = 0; u < 4; u++)
+#pragma unroll
+            for (int q = 0; q < N; q++) v[u][q] = (i + 256 * u < n) ? slots[N * (i + 256 * u) + q] : OP::identity();
+#pragma unroll
+        for (int u = 0; u < 4; u++)
+#pragma unroll
+            for (int q = 0; q < N; q++) out[q] = OP::apply(out[q], v[u][q]);
+    }
+#pragma unroll
+    for (int q = 0; q < N; q++) part[q][threadIdx.x] = out[q];
+    __syncthreads();
+    for (int w = 128; w >= 1; w >>= 1) {
+        if ((int)threadIdx.x < w)
+#pragma unroll
+            for (int q = 0; q < N; q++) part[q][threadIdx.x] = OP::apply(part[q][threadIdx.x], part[q][threadIdx.x + w]);
+        __syncthreads();
+    }
+#pragma unroll
+    for (int q = 0; q < N; q++) out[q] = part[q][0];
+}
 // slots a one-workgroup kernel sums: what the last sweep announced, as far as the buffer holds it
 __device__ __forceinline__ int ctl_nslots(const CtlHead &h) { return h.nslots < h.capacity ? h.nslots : h.capacity; }
 

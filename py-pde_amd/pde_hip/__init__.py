@@ -23,6 +23,7 @@ from .interpolation import interpolate_to_grid
 from .pdes import (PDE, AllenCahnPDE, CahnHilliardPDE, DiffusionPDE, KleinGordonPDE, KPZInterfacePDE, KuramotoSivashinskyPDE,
                    SwiftHohenbergPDE, WavePDE)
 from .poisson import solve_laplace_equation, solve_poisson_equation
+from .statistics import FieldStatistics, field_statistics
 from .solvers import Controller, ConvergenceError, CrankNicolsonSolver, EulerSolver, ExplicitSolver, ImplicitSolver, RungeKuttaSolver
 
 _operators.register_all(HipBackend, CartesianGrid)
@@ -45,6 +46,7 @@ __all__ = [
     "EulerSolver",
     "FieldCollection",
     "ExplicitSolver",
+    "FieldStatistics",
     "HipBackend",
     "ImplicitSolver",
     "RungeKuttaSolver",
@@ -52,6 +54,7 @@ __all__ = [
     "Tensor2Field",
     "UnitGrid",
     "VectorField",
+    "field_statistics",
     "get_backend",
     "interpolate_to_grid",
     "solve_laplace_equation",

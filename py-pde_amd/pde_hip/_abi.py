@@ -365,6 +365,9 @@ OPTIONAL_PROTOTYPES: dict[str, list] = {
     "laplace_f32p": [_pg, _vp, _vp, _i, _vp],
     "euler_run_f32p": [_pg, _pr, _vp, _vp, _d, _i64, _pvp, _vp],
     "f32p_supported": [_pg, _pr, C.POINTER(_i)],
+    # statistics of a field on the device and the steady-state test against a snapshot (csrc/pdehip_stats.hip)
+    "field_stats": [_pg, _i, _vp, _i, _i, _vp, _vp],
+    "steady_state": [_pg, _i, _vp, _vp, _d, _d, _vp, _vp],
 }
 
 

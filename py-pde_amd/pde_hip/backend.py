@@ -58,9 +58,10 @@ from .operators_glue import _NONLINEAR_OPERATORS, OperatorGlueMixin  # noqa: E40
 from .noise_hooks import NoiseHookMixin  # noqa: E402
 from .interpolation import InterpolationMixin  # noqa: E402
 from .steppers import StepperMixin  # noqa: E402
+from .statistics import StatisticsMixin  # noqa: E402
 
 
-class HipBackendMixin(OperatorGlueMixin, InterpolationMixin, RhsPlanningMixin, NoiseHookMixin, StepperMixin):
+class HipBackendMixin(OperatorGlueMixin, InterpolationMixin, StatisticsMixin, RhsPlanningMixin, NoiseHookMixin, StepperMixin):
     """Implementation shared by the stand-alone and the py-pde-plugin backend classes."""
 
     implementation = "hip"

@@ -119,6 +119,33 @@ class DataFieldBase:
 
         return get_backend(backend).interpolate_to_grid(self, grid, bc=bc, fill=fill, label=label)
 
+    # --- statistics (fields/datafield_base.py:846-897), host numpy; on the device: pde_hip/statistics.py ---------------------------------
+    @property
+    def integral(self):
+        """Integral of each component over space."""
+        from .statistics import host_integral
+
+        return host_integral(self.data, self.rank, self.grid.cell_volumes)
+
+    @property
+    def average(self):
+        """The integral of each component divided by the grid volume."""
+        return self.integral / self.grid.volume
+
+    @property
+    def fluctuations(self):
+        """Standard deviation of each component, of the data scaled by the square root of the cell volume."""
+        from .statistics import host_fluctuations
+
+        return host_fluctuations(self.data, self.rank, self.grid.cell_volumes)
+
+    @property
+    def magnitude(self) -> float:
+        """|average| of a scalar field; of the norm over the components for vector (more than one axis, or complex) and tensor fields."""
+        from .statistics import host_magnitude
+
+        return host_magnitude(self.data, self.rank, self.grid.num_axes, self.grid.cell_volumes, self.grid.volume)
+
     def apply_operator(self, operator: str, bc, out=None, *, label=None, args=None, backend="hip", **kwargs):
         """Apply a (differential) operator with BCs (fields/datafield_base.py:900-963)."""
         from .backend import get_backend
@@ -218,6 +245,18 @@ class FieldCollection:
 
     def __iter__(self):
         return iter(self._fields)
+
+    @property
+    def integrals(self) -> list:
+        return [f.integral for f in self._fields]
+
+    @property
+    def averages(self) -> list:
+        return [f.average for f in self._fields]
+
+    @property
+    def magnitudes(self) -> np.ndarray:
+        return np.array([f.magnitude for f in self._fields])
 
     def __len__(self) -> int:
         return len(self._fields)

@@ -65,6 +65,13 @@ DEFAULT_CONFIG = {
         description="Keep the state on the device between the calls of one stepper: tracker interrupts only download it, "
         "and it is uploaded again only when the host copy was modified in between.",
     ),
+    "device_statistics": Parameter(
+        value=False,
+        cls=bool,
+        description="Answer `integral`, `average`, `fluctuations` and `magnitude` of a state that is resident on the device from a device "
+        "reduction, without downloading it.  Off by default: a device sum differs from numpy's in the last bits.  The trackers "
+        "`hip_steady_state` and `hip_material_conservation` do not depend on it.",
+    ),
 }
 
 
@@ -387,6 +394,82 @@ class HipConsistencyTracker(_trackers.ConsistencyTracker):
             return super().handle(field, t)
         if not link.backend.make_finite_check()(field):
             msg = "Field was not finite"
+            raise StopIteration(msg)
+        return None
+
+
+class HipSteadyStateTracker(_trackers.SteadyStateTracker):
+    """``SteadyStateTracker`` (pde/trackers/trackers.py:748-875) that does not pull the state to the host: while the state is resident on
+    the device the rate of change is evaluated there against a snapshot that stays there too (``pdehip_steady_state``; the snapshot is
+    one more array of the state's size on the device).  Use ``tracker=["progress", "hip_steady_state"]`` or an instance of this class.
+    ``progress=True`` and ``evolution_rate=...`` take the parent's host path, and so does every state that is not resident (another
+    backend, decomposed steppers, a FieldCollection) or that the kernel does not take (complex fields)."""
+
+    name = "hip_steady_state"
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        from .statistics import SteadyStateCheck
+
+        self._check = SteadyStateCheck(None, self.atol, self.rtol)
+
+    def handle(self, field, t: float) -> None:
+        from .statistics import device_usable
+
+        link = getattr(field, "__dict__", {}).get("_hip_link")
+        check = self._check
+        on_device = (link is not None and link.host_stale and not self.progress and self.evolution_rate is None
+                     and device_usable(link.backend, link.dev_state))
+        if not on_device:
+            if check.started:                     # the snapshot goes back to where the parent keeps it
+                self._last_data, self._last_time = check.release()
+            return super().handle(field, t)
+        if not check.started and self._last_data is not None:
+            check.seed(self._last_data, self._last_time)      # the parent took it at an interrupt before the state became resident
+            self._last_data = None
+        check.atol, check.rtol = float(self.atol), float(self.rtol)
+        value = check.update(field, t)
+        if value is not None and check.converged(value):
+            msg = "Reached stationary state"
+            raise _trackers.FinishedSimulation(msg)
+        return None
+
+
+class HipMaterialConservationTracker(_trackers.MaterialConservationTracker):
+    """``MaterialConservationTracker`` (pde/trackers/trackers.py:1006-1065) whose magnitudes come from a device reduction
+    (``pdehip_field_stats``) while the state is resident on the device: |average| of a scalar field, of the norm over the components for
+    vector fields on more than one axis and for tensor fields; a FieldCollection field by field, through its component slices of the
+    device state.  The comparison stays ``np.isclose(magnitudes, reference, rtol, atol)``.  States that are not resident take the
+    parent's host path.  Use ``tracker=["hip_material_conservation"]`` or an instance of this class."""
+
+    name = "hip_material_conservation"
+
+    @staticmethod
+    def _device_magnitudes(field):
+        """The magnitudes from the device, or None where the host path applies."""
+        from .statistics import NOT_ANSWERED, device_property
+
+        link = getattr(field, "__dict__", {}).get("_hip_link")
+        if link is None or not link.host_stale:
+            return None
+        name = "magnitudes" if isinstance(field, pde.FieldCollection) else "magnitude"
+        value = device_property(link, field, name)
+        return None if value is NOT_ANSWERED else value
+
+    def initialize(self, field, info=None) -> float:
+        mags = self._device_magnitudes(field)
+        if mags is None:
+            return super().initialize(field, info)
+        self._reference = mags
+        return _trackers.TrackerBase.initialize(self, field, info)
+
+    def handle(self, field, t: float) -> None:
+        mags = self._device_magnitudes(field)
+        if mags is None:
+            return super().handle(field, t)
+        c = np.isclose(mags, self._reference, rtol=self.rtol, atol=self.atol)
+        if not np.all(c):
+            msg = f"Material of field {np.flatnonzero(~c)} is not conserved" if isinstance(field, pde.FieldCollection) else "Material is not conserved"
             raise StopIteration(msg)
         return None
 

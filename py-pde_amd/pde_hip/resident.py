@@ -30,6 +30,7 @@ def _config_get(config, key: str, default):
 
 
 _DATA_ATTRIBUTES = frozenset({"data", "_data_valid", "_data_full", "_FieldBase__data_full"})
+_STATISTICS_ATTRIBUTES = frozenset({"integral", "average", "fluctuations", "magnitude", "integrals", "averages", "magnitudes"})
 _SYNCED_CLASSES: dict[type, type] = {}
 
 
@@ -128,6 +129,16 @@ class ResidentState:
 
 def _make_synced_class(base: type) -> type:
     def __getattribute__(self, name):
+        if name in _STATISTICS_ATTRIBUTES:
+            # opt-in (`device_statistics`, default off): answered from the device copy while it is the current one - no download, and
+            # the class stays swapped in.  Whatever the kernels do not take falls through to the property, which reads `data` below.
+            link = object.__getattribute__(self, "__dict__").get("_hip_link")
+            if link is not None and link.host_stale and getattr(link.backend, "device_statistics", False):
+                from .statistics import NOT_ANSWERED, device_property
+
+                value = device_property(link, self, name)
+                if value is not NOT_ANSWERED:
+                    return value
         if name in _DATA_ATTRIBUTES:
             link = object.__getattribute__(self, "__dict__").get("_hip_link")
             if link is not None:
