@@ -895,6 +895,45 @@ int pdehip_field_stats(const pdehip_grid_t *g, int ncomp, const void *arr_full, 
 int pdehip_steady_state(const pdehip_grid_t *g, int ncomp, const void *cur_full, void *last_full, double elapsed, double rtol,
                         double *out_dev, void *stream);
 
+/* ---- projections and boxes of a field where it lives (optional entry points; the ABI version stays 8) ------------------------------
+ * The reduced-dimensional pictures a tracker writes out of a 3-D run, without moving the state to the host.  Both entries read the
+ * INTERIOR cells of a full array in the device layout (ghost cells and row padding never enter a result); arr_full is on a 16-byte
+ * boundary (what pdehip_malloc and the component pitch of pdehip_layout give).  No atomics: two calls give equal bits.
+ *
+ * pdehip_project: replaces `ScalarField.project` (pde/fields/scalar.py:269-339) on the arrays behind it: `grid.integrate(data, axes)`
+ * (pde/grids/base.py:1286-1341; a sum over the removed axes of data x cell volume) and `np.max` / `np.min` over the removed axes
+ * (pde/fields/scalar.py:325-329); `project_#` of `CartesianGrid.get_line_data` (pde/grids/cartesian.py:296-372) is the sum with weight 1,
+ * divided by the number of removed cells on the host.  Bit a of axes_mask removes axis a of the grid (the grid's own order); the mask
+ * is not empty and names no other axis; removing every axis leaves one value per component.  out_dev: a dense C-ordered array
+ * (ncomp, retained extents...).
+ *   PDEHIP_PROJECT_SUM   per output cell the sum of (double)x * weight over the removed cells; every term and every addition is one
+ *                        fp64 rounding (never FMA-contracted), the order is fixed by the shape.  Output: double for both field types
+ *                        (an fp32 array times the fp64 cell volumes is fp64 in numpy).  NaN and +-inf propagate by the arithmetic.
+ *   PDEHIP_PROJECT_MAX / _MIN   output in the field's own type, the bits of np.max / np.min: NaN if any removed cell of the output cell
+ *                        is NaN, +-inf are ordinary values; the sign of a zero result is unspecified when both zeros occur.  weight is
+ *                        ignored.
+ * Removing the fastest axis is a reduction of each row by a group of 1 ... 64 lanes; removing slower axes is a march of each thread
+ * over the removed cells in segments of 128, with whole pieces of rows read by the lanes of a wave at every step; the partial results
+ * (one per row, or one per segment and output cell) go through dense fp64 arrays that the same two kernels reduce further, in a fixed
+ * order.  These arrays are kept per stream, grown on demand and freed by pdehip_release_scratch. pdehip_last_kernel_name gives the
+ * chain of instances, joined by `+`.
+ *
+ * pdehip_extract_box: replaces the index expressions of `ScalarField.slice` (pde/fields/scalar.py:341-427), of `cut_#` in
+ * `CartesianGrid.get_line_data` and of `CartesianGrid.get_image_data` (pde/grids/cartesian.py:374-402): the interior box
+ * [lo, lo + extent) of every component as a dense C-ordered array (ncomp, extent...) of the field's type.  lo and extent have one
+ * entry per axis of the grid, in the grid's own order; the box lies inside the grid and no extent is 0.  A slice is a box of extent 1 on
+ * the removed axes.
+ *
+ * Both refuse (status PDEHIP_E_VALUE, message in pdehip_last_error) NULL pointers, ncomp outside 1 ... 64, an empty or foreign
+ * mask, an unknown method, a box that is not inside the grid and a misaligned array. */
+#define PDEHIP_PROJECT_SUM 0
+#define PDEHIP_PROJECT_MAX 1
+#define PDEHIP_PROJECT_MIN 2
+int pdehip_project(const pdehip_grid_t *g, int ncomp, const void *arr_full, int axes_mask, int method, double weight,
+                   void *out_dev, void *stream);
+int pdehip_extract_box(const pdehip_grid_t *g, int ncomp, const void *arr_full, const long *lo, const long *extent,
+                       void *out_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -542,7 +542,9 @@ int pdehip_comm_destroy(void *comm)
 int pdehip_release_scratch(void)
 {
     release_scratch(serial_context());
-    return stats_release_scratch();
+    const int rc = stats_release_scratch();
+    const int rc2 = project_release_scratch();
+    return rc ? rc : rc2;
 }
 
 // what RCCL itself says about the communicator: out5 = {ncclCommCount, ncclCommUserRank, ncclCommCuDevice, ncclGetVersion, HIP device of the

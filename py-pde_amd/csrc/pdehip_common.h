@@ -155,6 +155,7 @@ struct Euler2Plan {
 };
 int preload_shell_kernels();     // pdehip_shell.hip: the same for its code object
 int stats_release_scratch();     // pdehip_stats.hip: frees the per-stream slots of its sweeps (pdehip_release_scratch)
+int project_release_scratch();   // pdehip_project.hip: the same for the partial results of its stages
 #include "pdehip_launchers.h"
 namespace exactv {
 #include "pdehip_launchers.h"

@@ -23,6 +23,7 @@ from .interpolation import interpolate_to_grid
 from .pdes import (PDE, AllenCahnPDE, CahnHilliardPDE, DiffusionPDE, KleinGordonPDE, KPZInterfacePDE, KuramotoSivashinskyPDE,
                    SwiftHohenbergPDE, WavePDE)
 from .poisson import solve_laplace_equation, solve_poisson_equation
+from .projection import image_data, line_data, project, slice_field
 from .statistics import FieldStatistics, field_statistics
 from .solvers import Controller, ConvergenceError, CrankNicolsonSolver, EulerSolver, ExplicitSolver, ImplicitSolver, RungeKuttaSolver
 
@@ -56,7 +57,11 @@ __all__ = [
     "VectorField",
     "field_statistics",
     "get_backend",
+    "image_data",
     "interpolate_to_grid",
+    "line_data",
+    "project",
+    "slice_field",
     "solve_laplace_equation",
     "solve_poisson_equation",
 ]

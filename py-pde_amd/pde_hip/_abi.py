@@ -368,7 +368,12 @@ OPTIONAL_PROTOTYPES: dict[str, list] = {
     # statistics of a field on the device and the steady-state test against a snapshot (csrc/pdehip_stats.hip)
     "field_stats": [_pg, _i, _vp, _i, _i, _vp, _vp],
     "steady_state": [_pg, _i, _vp, _vp, _d, _d, _vp, _vp],
+    # sum / maximum / minimum over a subset of the axes, and dense copies of interior boxes (csrc/pdehip_project.hip)
+    "project": [_pg, _i, _vp, _i, _i, _d, _vp, _vp],
+    "extract_box": [_pg, _i, _vp, C.POINTER(C.c_long), C.POINTER(C.c_long), _vp, _vp],
 }
+
+PROJECT_SUM, PROJECT_MAX, PROJECT_MIN = 0, 1, 2
 
 
 def exported_symbols() -> list[str]:

@@ -59,9 +59,10 @@ from .noise_hooks import NoiseHookMixin  # noqa: E402
 from .interpolation import InterpolationMixin  # noqa: E402
 from .steppers import StepperMixin  # noqa: E402
 from .statistics import StatisticsMixin  # noqa: E402
+from .projection import ProjectionMixin  # noqa: E402
 
 
-class HipBackendMixin(OperatorGlueMixin, InterpolationMixin, StatisticsMixin, RhsPlanningMixin, NoiseHookMixin, StepperMixin):
+class HipBackendMixin(OperatorGlueMixin, InterpolationMixin, StatisticsMixin, ProjectionMixin, RhsPlanningMixin, NoiseHookMixin, StepperMixin):
     """Implementation shared by the stand-alone and the py-pde-plugin backend classes."""
 
     implementation = "hip"

@@ -174,6 +174,43 @@ class DataFieldBase:
 class ScalarField(DataFieldBase):
     rank = 0
 
+    # --- projections and cuts (fields/scalar.py:269-427, fields/datafield_base.py:1037-1074), host numpy; on the device: pde_hip/projection.py
+    def project(self, axes, *, method: str = "integral", label=None) -> "ScalarField":
+        """Remove ``axes`` by an integral, an average (``"average"`` / ``"mean"``), a maximum or a minimum."""
+        from .projection import host_project, parse_axes
+
+        ax_remove, ax_retain = parse_axes(self.grid, axes)
+        sliced = self.grid.slice(ax_retain)
+        return self.__class__(sliced, host_project(self.grid, self.data, ax_remove, method), label=label)
+
+    def slice(self, position, *, method: str = "nearest", label=None) -> "ScalarField":
+        """The cells nearest to ``position`` (axis name -> coordinate or ``"low"`` / ``"mid"`` / ``"high"``); the axes named are removed."""
+        from .projection import nearest_cells, parse_position
+
+        values, ax_retain = parse_position(self.grid, position)
+        sliced = self.grid.slice(ax_retain)
+        if method != "nearest":
+            msg = f"Unknown slicing method `{method}`"
+            raise ValueError(msg)
+        cells = nearest_cells(self.grid, values)
+        return self.__class__(sliced, self.data[tuple(cells.get(ax, slice(None)) for ax in range(self.grid.num_axes))], label=label)
+
+    def get_line_data(self, scalar: str = "auto", extract: str = "auto") -> dict:
+        from .projection import host_line_data, label_line
+
+        if scalar != "auto":
+            msg = "the mirror fields know scalar='auto' only"
+            raise NotImplementedError(msg)
+        return label_line(self, host_line_data(self.grid, self.data, extract))
+
+    def get_image_data(self, scalar: str = "auto", transpose: bool = False) -> dict:
+        from .projection import finish_image, host_image_data
+
+        if scalar != "auto":
+            msg = "the mirror fields know scalar='auto' only"
+            raise NotImplementedError(msg)
+        return finish_image(self, host_image_data(self.grid, self.data), transpose)
+
     def laplace(self, bc, out=None, **kwargs) -> "ScalarField":
         return self.apply_operator("laplace", bc=bc, out=out, **kwargs)
 

@@ -55,7 +55,11 @@ class CartesianGrid:
 
     @property
     def axes(self) -> list[str]:
-        return list(_AXES[: self.dim])
+        return list(getattr(self, "_axes", None) or _AXES[: self.dim])
+
+    @axes.setter
+    def axes(self, names) -> None:
+        self._axes = list(names)
 
     @property
     def shape(self) -> tuple[int, ...]:
@@ -96,6 +100,13 @@ class CartesianGrid:
     @property
     def _idx_valid(self) -> tuple[slice, ...]:
         return (slice(1, -1),) * self.dim
+
+    def slice(self, indices) -> "CartesianGrid":
+        """The subgrid of the axes ``indices``, which keep their names (cartesian.py:454-470)."""
+        sub = CartesianGrid([self._bounds[i] for i in indices], tuple(self._shape[i] for i in indices), [self._periodic[i] for i in indices])
+        sub.__class__ = self.__class__
+        sub.axes = [self.axes[i] for i in indices]
+        return sub
 
     def __eq__(self, other) -> bool:
         return (

@@ -72,6 +72,13 @@ DEFAULT_CONFIG = {
         "reduction, without downloading it.  Off by default: a device sum differs from numpy's in the last bits.  The trackers "
         "`hip_steady_state` and `hip_material_conservation` do not depend on it.",
     ),
+    "device_projections": Parameter(
+        value=False,
+        cls=bool,
+        description="Answer `project`, `slice`, `get_line_data` and `get_image_data` of a real scalar field whose state is resident on the "
+        "device from a device reduction or copy, without downloading the state.  Off by default: a device sum differs from numpy's in the "
+        "last bits.  `pde_hip.project`, `pde_hip.slice_field`, `pde_hip.line_data` and `pde_hip.image_data` do not depend on it.",
+    ),
 }
 
 

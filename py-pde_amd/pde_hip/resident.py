@@ -31,6 +31,7 @@ def _config_get(config, key: str, default):
 
 _DATA_ATTRIBUTES = frozenset({"data", "_data_valid", "_data_full", "_FieldBase__data_full"})
 _STATISTICS_ATTRIBUTES = frozenset({"integral", "average", "fluctuations", "magnitude", "integrals", "averages", "magnitudes"})
+_PROJECTION_METHODS = frozenset({"project", "slice", "get_line_data", "get_image_data"})
 _SYNCED_CLASSES: dict[type, type] = {}
 
 
@@ -139,6 +140,16 @@ def _make_synced_class(base: type) -> type:
                 value = device_property(link, self, name)
                 if value is not NOT_ANSWERED:
                     return value
+        if name in _PROJECTION_METHODS:
+            # opt-in (`device_projections`, default off): projections, slices and the data behind line and image plots of a real scalar
+            # field come from the device copy.  Whatever the device path does not take goes to the reference method, which reads `data`.
+            link = object.__getattribute__(self, "__dict__").get("_hip_link")
+            if link is not None and link.host_stale and getattr(link.backend, "device_projections", False):
+                from .projection import device_method
+
+                method = device_method(link, self, name)
+                if method is not None:
+                    return method
         if name in _DATA_ATTRIBUTES:
             link = object.__getattribute__(self, "__dict__").get("_hip_link")
             if link is not None:
