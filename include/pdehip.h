@@ -934,6 +934,43 @@ int pdehip_project(const pdehip_grid_t *g, int ncomp, const void *arr_full, int 
 int pdehip_extract_box(const pdehip_grid_t *g, int ncomp, const void *arr_full, const long *lo, const long *extent,
                        void *out_dev, void *stream);
 
+/* ---- Gaussian smoothing of a field where it lives: one pass along one axis (optional entry point; the ABI version stays 8) -----------
+ * Replaces one call of `scipy.ndimage.gaussian_filter1d` in `DataFieldBase.smooth` (pde/fields/datafield_base.py:988-1035) on the
+ * arrays behind it; the caller chains one pass per axis (pde_hip/smoothing.py).  Bit for bit scipy's result, given scipy's weights.
+ *
+ * One pass filters axis `axis` (the grid's own order) of extent n with radius r >= 0 and the weights w[0..r], w[0] the centre weight
+ * (the upper half of the symmetric kernel).  For every interior cell i along that axis, in fp64:
+ *
+ *     t = x[i] * w[0]
+ *     for j = r, r-1, ..., 1:   t = t + (x[idx(i-j)] + x[idx(i+j)]) * w[j]
+ *     out[i] = t
+ *
+ * Every product and every addition is one fp64 rounding, never contracted into an FMA (scipy's symmetric branch, its line buffers are
+ * double).  An fp32 field is converted exactly to fp64 on load and rounded once to fp32 on store - in both settings of the fp32
+ * arithmetic mode.  idx(p) holds for ANY r, including r >= n, r >= 2n and n == 1:
+ *     PDEHIP_SMOOTH_WRAP      p mod n                                       (mode "wrap": periodic axes)
+ *     PDEHIP_SMOOTH_REFLECT   q = p mod 2n, then q < n ? q : 2n - 1 - q     (mode "reflect": scipy's half-sample symmetric extension)
+ * with the mathematical (non-negative) modulus.  r == 0 is the copy x * w[0].  NaN and +-inf propagate by the arithmetic.  Only
+ * INTERIOR cells of the full device layout are read and written: ghost cells and row padding of out_full are left as they were, and
+ * in_full is not modified.  No atomics: two calls give equal bits.
+ *
+ * weights: HOST memory, radius + 1 values, consumed before the call returns (they are staged in per-stream scratch that
+ * pdehip_release_scratch frees).  They come from the host because numpy's exp is the one scipy uses and libm's may differ in the last
+ * bit: pde_hip/smoothing.py::gaussian_weights.
+ *
+ * Instances (pdehip_last_kernel_name names the one that ran): `gauss_row_kernel<T>` filters the fastest axis through LDS, radius up to
+ * 608; `gauss_march_kernel<T,VEC>` any slower axis through LDS, radius up to 48 (VEC = 2 doubles / 4 floats per lane where the row
+ * length is a multiple of that, else 1); `gauss_cell_kernel<T>` takes everything else: any radius, axis and extent, one output cell per
+ * thread.  PDEHIP_SMOOTH_CELL or'ed into the mode forces the last one (the yardstick of the tests).
+ *
+ * Refused (status PDEHIP_E_VALUE, message in pdehip_last_error): NULL pointers, ncomp outside 1 ... 64, an axis the grid does not have,
+ * an unknown mode, radius < 0, in_full == out_full or overlapping arrays, an array that is not on a 16-byte boundary. */
+#define PDEHIP_SMOOTH_WRAP    0
+#define PDEHIP_SMOOTH_REFLECT 1
+#define PDEHIP_SMOOTH_CELL    16   /* or'ed into mode: force the one-cell-per-thread instance (the yardstick of the tests) */
+int pdehip_smooth_axis(const pdehip_grid_t *g, int ncomp, const void *in_full, void *out_full, int axis, int mode,
+                       int radius, const double *weights /* host, radius + 1 values, consumed before return */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -544,7 +544,8 @@ int pdehip_release_scratch(void)
     release_scratch(serial_context());
     const int rc = stats_release_scratch();
     const int rc2 = project_release_scratch();
-    return rc ? rc : rc2;
+    const int rc3 = smooth_release_scratch();
+    return rc ? rc : (rc2 ? rc2 : rc3);
 }
 
 // what RCCL itself says about the communicator: out5 = {ncclCommCount, ncclCommUserRank, ncclCommCuDevice, ncclGetVersion, HIP device of the

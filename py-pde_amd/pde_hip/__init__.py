@@ -24,6 +24,7 @@ from .pdes import (PDE, AllenCahnPDE, CahnHilliardPDE, DiffusionPDE, KleinGordon
                    SwiftHohenbergPDE, WavePDE)
 from .poisson import solve_laplace_equation, solve_poisson_equation
 from .projection import image_data, line_data, project, slice_field
+from .smoothing import smooth
 from .statistics import FieldStatistics, field_statistics
 from .solvers import Controller, ConvergenceError, CrankNicolsonSolver, EulerSolver, ExplicitSolver, ImplicitSolver, RungeKuttaSolver
 
@@ -62,6 +63,7 @@ __all__ = [
     "line_data",
     "project",
     "slice_field",
+    "smooth",
     "solve_laplace_equation",
     "solve_poisson_equation",
 ]

@@ -371,9 +371,12 @@ OPTIONAL_PROTOTYPES: dict[str, list] = {
     # sum / maximum / minimum over a subset of the axes, and dense copies of interior boxes (csrc/pdehip_project.hip)
     "project": [_pg, _i, _vp, _i, _i, _d, _vp, _vp],
     "extract_box": [_pg, _i, _vp, C.POINTER(C.c_long), C.POINTER(C.c_long), _vp, _vp],
+    # one pass of a separable Gaussian filter along one axis, weights from the host (csrc/pdehip_smooth.hip)
+    "smooth_axis": [_pg, _i, _vp, _vp, _i, _i, _i, _pd, _vp],
 }
 
 PROJECT_SUM, PROJECT_MAX, PROJECT_MIN = 0, 1, 2
+SMOOTH_WRAP, SMOOTH_REFLECT, SMOOTH_CELL = 0, 1, 16
 
 
 def exported_symbols() -> list[str]:

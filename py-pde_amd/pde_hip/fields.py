@@ -146,6 +146,13 @@ class DataFieldBase:
 
         return host_magnitude(self.data, self.rank, self.grid.num_axes, self.grid.cell_volumes, self.grid.volume)
 
+    # --- Gaussian smoothing (fields/datafield_base.py:988-1035), host numpy; on the device: pde_hip/smoothing.py -----------------------
+    def smooth(self, sigma: float = 1, *, out=None, label=None):
+        """Gaussian filter of standard deviation ``sigma`` (a length): wrap on periodic axes, reflect elsewhere; ``out=self``: in place."""
+        from .smoothing import mirror_smooth
+
+        return mirror_smooth(self, sigma, out=out, label=label)
+
     def apply_operator(self, operator: str, bc, out=None, *, label=None, args=None, backend="hip", **kwargs):
         """Apply a (differential) operator with BCs (fields/datafield_base.py:900-963)."""
         from .backend import get_backend
@@ -303,3 +310,9 @@ class FieldCollection:
 
     def copy(self, *, label=None, dtype=None):
         return FieldCollection([f.copy() for f in self._fields], dtype=dtype or self.dtype)
+
+    def smooth(self, sigma: float = 1, *, out=None, label=None) -> "FieldCollection":
+        """Every field smoothed on its own (``pde/fields/collection.py:673-710``)."""
+        from .smoothing import mirror_smooth_collection
+
+        return mirror_smooth_collection(self, sigma, out=out, label=label)

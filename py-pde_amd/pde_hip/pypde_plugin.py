@@ -79,6 +79,13 @@ DEFAULT_CONFIG = {
         "device from a device reduction or copy, without downloading the state.  Off by default: a device sum differs from numpy's in the "
         "last bits.  `pde_hip.project`, `pde_hip.slice_field`, `pde_hip.line_data` and `pde_hip.image_data` do not depend on it.",
     ),
+    "device_smoothing": Parameter(
+        value=False,
+        cls=bool,
+        description="Run `smooth` of a real field whose state is resident on the device there, without downloading the state: only a "
+        "host result comes down, and `out=state` smooths in place on the device.  The bits are scipy's either way; off by default so "
+        "that nothing changes its path unasked.  `pde_hip.smooth` does not depend on it.",
+    ),
 }
 
 

@@ -32,6 +32,7 @@ def _config_get(config, key: str, default):
 _DATA_ATTRIBUTES = frozenset({"data", "_data_valid", "_data_full", "_FieldBase__data_full"})
 _STATISTICS_ATTRIBUTES = frozenset({"integral", "average", "fluctuations", "magnitude", "integrals", "averages", "magnitudes"})
 _PROJECTION_METHODS = frozenset({"project", "slice", "get_line_data", "get_image_data"})
+_SMOOTHING_METHODS = frozenset({"smooth"})
 _SYNCED_CLASSES: dict[type, type] = {}
 
 
@@ -148,6 +149,16 @@ def _make_synced_class(base: type) -> type:
                 from .projection import device_method
 
                 method = device_method(link, self, name)
+                if method is not None:
+                    return method
+        if name in _SMOOTHING_METHODS:
+            # opt-in (`device_smoothing`, default off): `smooth` of a real field runs on the device copy; only a host result comes down.
+            # Whatever the device path does not take goes to the reference method, which reads `data`.
+            link = object.__getattribute__(self, "__dict__").get("_hip_link")
+            if link is not None and link.host_stale and getattr(link.backend, "device_smoothing", False):
+                from .smoothing import device_method as smoothing_method
+
+                method = smoothing_method(link, self, name)
                 if method is not None:
                     return method
         if name in _DATA_ATTRIBUTES:
