@@ -971,6 +971,46 @@ int pdehip_extract_box(const pdehip_grid_t *g, int ncomp, const void *arr_full, 
 int pdehip_smooth_axis(const pdehip_grid_t *g, int ncomp, const void *in_full, void *out_full, int axis, int mode,
                        int radius, const double *weights /* host, radius + 1 values, consumed before return */, void *stream);
 
+/* ---- the distribution of a field where it lives: histogram and exact order statistics (optional entry points; the ABI version stays 8) --
+ * What `np.histogram(state.data)` and `np.quantile(state.data, q)` in a tracker callback answer, without moving the state to the host.
+ * Both entries read the INTERIOR cells of full arrays in the device layout (ghost cells and row padding never enter a result), sweep
+ * with 16-byte loads where the row length allows, and take 1 <= ncomp <= 64.  Without norm there is one block of results per component;
+ * norm != 0: ONE block for s = sqrt(x_0 * x_0 + x_1 * x_1 + ...) over the components, evaluated as pdehip_field_stats evaluates it.
+ * The results are integers and elements of the field: they do not depend on the order of evaluation, two calls give equal bits.  The
+ * workgroups count in 32-bit LDS counters (lanes of a wave that hit the same counter are combined first) and fold them with 64-bit
+ * integer adds in global memory.  Pinned host memory for the edges and the control blocks of the selection are kept per stream and
+ * freed by pdehip_release_scratch.  pdehip_last_kernel_name names the instance of the sweep.
+ *
+ * pdehip_histogram: edges_dev holds nbins + 1 fp64 edges e[0] < e[1] < ... < e[nbins], all finite, 1 <= nbins <= 4096.  Every block
+ * receives nbins + 3 unsigned 64-bit counts at counts_dev + block * (nbins + 3):
+ *     count[i], i < nbins   the cells with e[i] <= x < e[i + 1]; the last bin also takes x == e[nbins]
+ *     count[nbins]          the cells below e[0] (-inf included)
+ *     count[nbins + 1]      the cells above e[nbins] (+inf included)
+ *     count[nbins + 2]      the cells that are NaN
+ * Comparisons are in fp64 on the exactly converted value; the sum of a block is the number of interior cells.  The definition is by
+ * the edges alone: the kernel guesses a bin (a scaled subtraction where the bins are equal, a binary search else) and settles the guess
+ * by comparing with the edges, which gives the counts of `np.histogram` for `bins=int, range=...` with the edges numpy returns and for
+ * explicit edge arrays.  The edges are read back and checked on the host before the sweep is launched (the call waits for the stream).
+ *
+ * pdehip_quantile_select: q_host holds 1 <= nq <= 8 values in [0, 1] (HOST memory, consumed before the call returns).  For every block
+ * and every q[j], with n the number of cells that are not NaN, v = (n - 1) * q[j] in fp64 and k = floor(v):
+ *     lower_dev[block * nq + j]   the k-th smallest such cell (k = 0: the minimum)
+ *     upper_dev[block * nq + j]   the min(k + 1, n - 1)-th
+ * both in the field's own type and with the bits of an element of the field; +-inf are ordinary values; when +0 and -0 both occur the
+ * sign of a zero result is unspecified.  info_dev + 2 * block receives {n, number of NaN cells} as unsigned 64-bit integers.  n == 0:
+ * lower and upper are NaN.  Method: radix selection on the order-preserving integer image of the value bits, 8-bit digits from the top -
+ * 8 sweeps for fp64, 4 for fp32, all q in the same sweeps.  Each sweep counts, per digit value, the cells whose leading digits match a
+ * target's; a one-workgroup kernel behind it picks the next digit and the remaining rank of every target in a control block on the
+ * device.  The host does not synchronise between the passes (or at all).
+ *
+ * Both refuse (status PDEHIP_E_VALUE, message in pdehip_last_error) NULL pointers, ncomp outside 1 ... 64, nbins outside 1 ... 4096,
+ * nq outside 1 ... 8, a q outside [0, 1], edges that are not finite or not strictly increasing, and a misaligned array (16 bytes for
+ * the field, 8 for edges, counts and info, the element size for lower and upper). */
+int pdehip_histogram(const pdehip_grid_t *g, int ncomp, const void *arr_full, int norm, int nbins, const double *edges_dev,
+                     uint64_t *counts_dev, void *stream);
+int pdehip_quantile_select(const pdehip_grid_t *g, int ncomp, const void *arr_full, int norm, int nq, const double *q_host,
+                           void *lower_dev, void *upper_dev, uint64_t *info_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

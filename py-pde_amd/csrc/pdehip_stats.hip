@@ -10,38 +10,12 @@
 #include <mutex>
 
 #include "pdehip_common.h"
+#include "pdehip_pieces.h"
 #include "pdehip_sweep.h"
 
 namespace pdehip {
 namespace {
 
-// VEC cells of a row in one access (VEC > 1: the address is a multiple of 16 bytes - rows start on 128-byte lines, the callers check the
-// base pointers)
-template <typename T, int VEC>
-__device__ __forceinline__ void load_piece(const T *p, T (&v)[VEC])
-{
-    if constexpr (VEC == 1) {
-        v[0] = p[0];
-    } else {
-        typedef T vec_t __attribute__((ext_vector_type(VEC)));
-        const vec_t x = *(const vec_t *)p;
-#pragma unroll
-        for (int q = 0; q < VEC; q++) v[q] = x[q];
-    }
-}
-template <typename T, int VEC>
-__device__ __forceinline__ void store_piece(T *p, const T (&v)[VEC])
-{
-    if constexpr (VEC == 1) {
-        p[0] = v[0];
-    } else {
-        typedef T vec_t __attribute__((ext_vector_type(VEC)));
-        vec_t x;
-#pragma unroll
-        for (int q = 0; q < VEC; q++) x[q] = v[q];
-        *(vec_t *)p = x;
-    }
-}
 __device__ __forceinline__ double quiet_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
 
 struct StatsArgs {
@@ -54,24 +28,11 @@ struct StatsArgs {
     double *out;           // the block of eight of this component
 };
 
-// the values of one piece: the cells themselves, or s = sqrt(x_0 * x_0 + x_1 * x_1 + ...) in the field's type, one rounding per operation
+// the values of one piece (pdehip_pieces.h): the cells themselves, or the norm over the components
 template <typename T, int VEC, bool NORM>
 __device__ __forceinline__ void piece_values(const StatsArgs &a, long e, T (&v)[VEC])
 {
-    const T *in = (const T *)a.in + e;
-    load_piece<T, VEC>(in, v);
-    if (NORM) {
-#pragma unroll
-        for (int q = 0; q < VEC; q++) v[q] = v[q] * v[q];
-        for (int c = 1; c < a.ncomp; c++) {
-            T x[VEC];
-            load_piece<T, VEC>(in + c * a.pc, x);
-#pragma unroll
-            for (int q = 0; q < VEC; q++) v[q] = v[q] + x[q] * x[q];
-        }
-#pragma unroll
-        for (int q = 0; q < VEC; q++) v[q] = sqrt(v[q]);
-    }
+    pdehip::piece_values<T, VEC, NORM>((const T *)a.in + e, a.pc, a.ncomp, v);
 }
 
 // first sweep: the finite cells' count, sum, minimum and maximum (fp64, from values converted exactly) and the count of the others
@@ -216,14 +177,6 @@ int stats_scratch(hipStream_t st, StatsScratch *s)
     s->sums = it->second;
     s->pairs = it->second + 3L * kSweepWavesMax;
     return 0;
-}
-
-// cells per access: 16 bytes where the rows and the arrays allow
-int piece_width(const NGrid &n, const void *a, const void *b)
-{
-    if ((((uintptr_t)a | (uintptr_t)b) & 15) != 0) return 1;
-    if (n.dtype == PDEHIP_F64) return n.n[2] % 2 == 0 ? 2 : 1;
-    return n.n[2] % 4 == 0 ? 4 : 1;
 }
 
 template <bool NORM>

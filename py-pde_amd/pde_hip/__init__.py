@@ -17,6 +17,7 @@ library or a device is missing (there is no CPU fallback).
 from . import operators as _operators
 from .backend import HipBackend, get_backend
 from .boundaries import BoundariesList
+from .distribution import FieldHistogram, field_histogram, field_median, field_quantile
 from .fields import FieldCollection, ScalarField, Tensor2Field, VectorField
 from .grids import CartesianGrid, UnitGrid
 from .interpolation import interpolate_to_grid
@@ -48,6 +49,7 @@ __all__ = [
     "EulerSolver",
     "FieldCollection",
     "ExplicitSolver",
+    "FieldHistogram",
     "FieldStatistics",
     "HipBackend",
     "ImplicitSolver",
@@ -56,6 +58,9 @@ __all__ = [
     "Tensor2Field",
     "UnitGrid",
     "VectorField",
+    "field_histogram",
+    "field_median",
+    "field_quantile",
     "field_statistics",
     "get_backend",
     "image_data",

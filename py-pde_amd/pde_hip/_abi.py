@@ -373,6 +373,9 @@ OPTIONAL_PROTOTYPES: dict[str, list] = {
     "extract_box": [_pg, _i, _vp, C.POINTER(C.c_long), C.POINTER(C.c_long), _vp, _vp],
     # one pass of a separable Gaussian filter along one axis, weights from the host (csrc/pdehip_smooth.hip)
     "smooth_axis": [_pg, _i, _vp, _vp, _i, _i, _i, _pd, _vp],
+    # histogram over given edges and exact order statistics of a field on the device (csrc/pdehip_hist.hip)
+    "histogram": [_pg, _i, _vp, _i, _i, _vp, _vp, _vp],
+    "quantile_select": [_pg, _i, _vp, _i, _i, _pd, _vp, _vp, _vp, _vp],
 }
 
 PROJECT_SUM, PROJECT_MAX, PROJECT_MIN = 0, 1, 2

@@ -61,9 +61,10 @@ from .steppers import StepperMixin  # noqa: E402
 from .statistics import StatisticsMixin  # noqa: E402
 from .projection import ProjectionMixin  # noqa: E402
 from .smoothing import SmoothingMixin  # noqa: E402
+from .distribution import DistributionMixin  # noqa: E402
 
 
-class HipBackendMixin(OperatorGlueMixin, InterpolationMixin, StatisticsMixin, ProjectionMixin, SmoothingMixin, RhsPlanningMixin, NoiseHookMixin, StepperMixin):
+class HipBackendMixin(OperatorGlueMixin, InterpolationMixin, StatisticsMixin, ProjectionMixin, SmoothingMixin, DistributionMixin, RhsPlanningMixin, NoiseHookMixin, StepperMixin):
     """Implementation shared by the stand-alone and the py-pde-plugin backend classes."""
 
     implementation = "hip"
