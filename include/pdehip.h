@@ -1011,6 +1011,39 @@ int pdehip_histogram(const pdehip_grid_t *g, int ncomp, const void *arr_full, in
 int pdehip_quantile_select(const pdehip_grid_t *g, int ncomp, const void *arr_full, int norm, int nq, const double *q_host,
                            void *lower_dev, void *upper_dev, uint64_t *info_dev, void *stream);
 
+/* ---- the domains of a field where it lives: connected components and their sizes (optional entry points; the ABI version stays 8) -------
+ * What `scipy.ndimage.label(state.data > c0)` followed by `np.bincount` in a tracker callback answers (how many droplets, how large is
+ * each), without moving the state to the host.  All results are integers: they equal scipy's, two calls give equal bits.
+ *
+ * pdehip_label_domains reads the INTERIOR cells of ONE real component in the device layout (fp64 or fp32, 1-D to 3-D; ghost cells and
+ * row padding never enter).  A cell is FOREGROUND iff lo <= x <= hi, compared in fp64 on the exactly converted value; infinite bounds
+ * are allowed, a NaN cell is background.  Two foreground cells are neighbours if they differ by one step along one axis (connectivity
+ * 1: the 2 ndim face neighbours) or by at most one step along every axis (connectivity ndim: all 3^ndim - 1 neighbours,
+ * `generate_binary_structure(ndim, ndim)`); an axis a with periodic_host[a] != 0 (ndim ints in HOST memory, consumed before the call
+ * returns) wraps, corners included under full connectivity.  A domain is a class of the transitive closure.
+ *     labels_dev   dense C-ordered int32 array of the interior shape (no ghost cells, no pitch): 0 for background, 1 ... K for the
+ *                  cells of a domain; domains are numbered in the C order of their FIRST cell (scipy's numbering)
+ *     info_dev     {K, number of foreground cells} as unsigned 64-bit integers
+ * Method: union-find in which the root of a domain is its smallest linear cell index (parent[i] <= i always, so every walk to a root
+ * goes down and ends).  `label_tile_kernel<T,FULL>` labels tiles of 4 x 8 x 32 cells in LDS, `label_seam_kernel<FULL>` unites across
+ * tile faces, edges, corners and the periodic wrap with relaxed agent-scope atomics only (atomicMin on the larger root), a flatten
+ * kernel writes every cell's root to labels_dev, roots are counted per chunk of 4096 cells, one workgroup scans the counts, and the
+ * labels are written: no ticket counter, the order in which workgroups run does not enter.  Scratch memory - the parent array, 4 bytes
+ * per cell, and the chunk counts - is kept per stream and freed by pdehip_release_scratch.  A stream's first call, and a call on a grid with more cells than any
+ * before on that stream, allocates (and frees the smaller arrays), which waits for the device; every other call synchronises nothing.
+ * pdehip_last_kernel_name names the instance of the tile kernel.
+ * Refused (status PDEHIP_E_VALUE, message in pdehip_last_error): NULL pointers, lo > hi or a NaN bound, a connectivity other than 1 or
+ * ndim, more than 2^31 - 1 interior cells, a misaligned array (16 bytes for the field, 4 for the labels, 8 for info).
+ *
+ * pdehip_domain_sizes: sizes_dev[k], k < ndomains, receives the number of the ncells cells of labels_dev with label k + 1 (unsigned
+ * 64-bit; integer adds, the lanes of a wave that hit the same label combined first).  ndomains == 0 writes nothing (sizes_dev may be
+ * NULL).  Labels outside 0 ... ndomains are counted, never used as an index: if there is one the call is refused with their number
+ * (PDEHIP_E_VALUE) and sizes_dev holds the counts of the labels in range.  The call waits for the stream (the caller reads the sizes
+ * next).  Also refused: NULL pointers, ncells < 1, ndomains outside 0 ... 2^31 - 1, a misaligned array (4 bytes / 8 bytes). */
+int pdehip_label_domains(const pdehip_grid_t *g, const void *arr_full, double lo, double hi, int connectivity,
+                         const int *periodic_host, int32_t *labels_dev, uint64_t *info_dev, void *stream);
+int pdehip_domain_sizes(const int32_t *labels_dev, int64_t ncells, int64_t ndomains, uint64_t *sizes_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -546,7 +546,8 @@ int pdehip_release_scratch(void)
     const int rc2 = project_release_scratch();
     const int rc3 = smooth_release_scratch();
     const int rc4 = hist_release_scratch();
-    return rc ? rc : (rc2 ? rc2 : (rc3 ? rc3 : rc4));
+    const int rc5 = label_release_scratch();
+    return rc ? rc : (rc2 ? rc2 : (rc3 ? rc3 : (rc4 ? rc4 : rc5)));
 }
 
 // what RCCL itself says about the communicator: out5 = {ncclCommCount, ncclCommUserRank, ncclCommCuDevice, ncclGetVersion, HIP device of the

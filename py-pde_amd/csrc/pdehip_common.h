@@ -158,6 +158,7 @@ int stats_release_scratch();     // pdehip_stats.hip: frees the per-stream slots
 int project_release_scratch();   // pdehip_project.hip: the same for the partial results of its stages
 int smooth_release_scratch();    // pdehip_smooth.hip: the same for the staged weights of its passes
 int hist_release_scratch();      // pdehip_hist.hip: the same for the partial histograms, staged edges and control blocks
+int label_release_scratch();     // pdehip_label.hip: the same for the parent array, the chunk counts of the scan and the counter of refused labels
 #include "pdehip_launchers.h"
 namespace exactv {
 #include "pdehip_launchers.h"

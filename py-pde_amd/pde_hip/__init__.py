@@ -18,6 +18,7 @@ from . import operators as _operators
 from .backend import HipBackend, get_backend
 from .boundaries import BoundariesList
 from .distribution import FieldHistogram, field_histogram, field_median, field_quantile
+from .domains import FieldDomains, field_domains
 from .fields import FieldCollection, ScalarField, Tensor2Field, VectorField
 from .grids import CartesianGrid, UnitGrid
 from .interpolation import interpolate_to_grid
@@ -49,6 +50,7 @@ __all__ = [
     "EulerSolver",
     "FieldCollection",
     "ExplicitSolver",
+    "FieldDomains",
     "FieldHistogram",
     "FieldStatistics",
     "HipBackend",
@@ -58,6 +60,7 @@ __all__ = [
     "Tensor2Field",
     "UnitGrid",
     "VectorField",
+    "field_domains",
     "field_histogram",
     "field_median",
     "field_quantile",

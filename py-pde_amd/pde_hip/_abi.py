@@ -376,6 +376,9 @@ OPTIONAL_PROTOTYPES: dict[str, list] = {
     # histogram over given edges and exact order statistics of a field on the device (csrc/pdehip_hist.hip)
     "histogram": [_pg, _i, _vp, _i, _i, _vp, _vp, _vp],
     "quantile_select": [_pg, _i, _vp, _i, _i, _pd, _vp, _vp, _vp, _vp],
+    # connected domains of the cells inside an interval, numbered like scipy.ndimage.label, and their sizes (csrc/pdehip_label.hip)
+    "label_domains": [_pg, _vp, _d, _d, _i, C.POINTER(_i), _vp, _vp, _vp],
+    "domain_sizes": [_vp, _i64, _i64, _vp, _vp],
 }
 
 PROJECT_SUM, PROJECT_MAX, PROJECT_MIN = 0, 1, 2

@@ -62,9 +62,10 @@ from .statistics import StatisticsMixin  # noqa: E402
 from .projection import ProjectionMixin  # noqa: E402
 from .smoothing import SmoothingMixin  # noqa: E402
 from .distribution import DistributionMixin  # noqa: E402
+from .domains import DomainsMixin  # noqa: E402
 
 
-class HipBackendMixin(OperatorGlueMixin, InterpolationMixin, StatisticsMixin, ProjectionMixin, SmoothingMixin, DistributionMixin, RhsPlanningMixin, NoiseHookMixin, StepperMixin):
+class HipBackendMixin(OperatorGlueMixin, InterpolationMixin, StatisticsMixin, ProjectionMixin, SmoothingMixin, DistributionMixin, DomainsMixin, RhsPlanningMixin, NoiseHookMixin, StepperMixin):
     """Implementation shared by the stand-alone and the py-pde-plugin backend classes."""
 
     implementation = "hip"
