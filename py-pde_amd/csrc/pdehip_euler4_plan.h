@@ -46,6 +46,14 @@ constexpr int read_index(int level, int kind, int patch)
          : kind < RD_RIGHT0  ? image_index(level, kind - RD_LEFT0, 1, patch - 1)
                              : image_index(level, kind - RD_RIGHT0, 0, patch + 1);
 }
+// x - 2 * c in ONE instruction.  The reference computes vm = 2 * c and then x - vm (cartesian.py:220-227): two roundings on paper, but doubling
+// is exact, so x - vm is the real number x - 2c rounded once - which is what the fused multiply-add returns.  Bit for bit the same for all
+// finite c up to half the largest double (beyond it 2 * c overflows to infinity and the fused form does not; tests/test_euler4_fma.py walks
+// zeros of both signs, subnormals, cancellations and the largest magnitudes through a CPU probe).  Three of these per cell replace one
+// doubling and three subtractions: 10 instead of 11 fp64 instructions per cell and level in the kernel of pdehip_march4.inc.  (A macro: the
+// one form of an expression that the kernel and the host probe can share from a header without HIP qualifiers.)
+#define PDEHIP_E4_MINUS_TWICE(x, c) __builtin_fma(-2.0, (c), (x))
+
 constexpr long MIN_CHUNK = 8;       // the fewest output planes of an x-chunk (each chunk recomputes 2 * HALO planes more)
 constexpr long WANT_CHUNK = 16;     // chunks are not made shorter than this to fill the chip
 constexpr long CUS = 256;           // one workgroup per CU (LDS)

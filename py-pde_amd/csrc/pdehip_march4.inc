@@ -33,7 +33,10 @@
 // the workgroup alone.
 //
 // Per cell the arithmetic is `laplace` + `update` of pdehip_march2.inc (cartesian.py:220-227) in the same order: bit-identical to four single
-// steps in the exact build.
+// steps in the exact build.  One thing is written differently: each `neighbour - 2 * centre` is one fused multiply-add (PDEHIP_E4_MINUS_TWICE:
+// the doubling is exact, so the bits are the same) instead of a doubling shared by the three axes and a subtraction each - 10 fp64 instructions
+// per cell and level where there were 11.  The kernel's time follows its fp64 instruction count (the fp64 pipe is busy for more than half of a
+// launch and nothing that was rescheduled around it moved the time; profiles/euler4_vmcnt_time.md).
 template <typename T, int M2>
 __global__ void __launch_bounds__(e4plan::THREADS) euler4_kernel(const LapArgs a)
 {
@@ -78,14 +81,12 @@ __global__ void __launch_bounds__(e4plan::THREADS) euler4_kernel(const LapArgs a
     if ((int)threadIdx.x < GUARD) lds[threadIdx.x] = lds[IMAGE - GUARD + threadIdx.x] = 0;   // (no result depends on it)
 
     auto update = [&](double xm, double xp, double up, double dn, double left, double right, double cen) {
-        const double vm = 2 * cen;
-        if (M2 == E2_DIFFUSION_UNIT) {   // all scales are exactly 1.0
-            const double ex = xm - vm + xp, ey = up - vm + dn, ez = left - vm + right;
-            return cen + a.s2 * (ex + ey + ez);
-        }
-        const double ex = (xm - vm + xp) * a.sx;
-        const double ey = (up - vm + dn) * a.sy;
-        const double ez = (left - vm + right) * a.sz;
+        // (xm - 2 * cen) + xp and so on, as the reference rounds them
+        const double dx = PDEHIP_E4_MINUS_TWICE(xm, cen) + xp, dy = PDEHIP_E4_MINUS_TWICE(up, cen) + dn, dz = PDEHIP_E4_MINUS_TWICE(left, cen) + right;
+        if (M2 == E2_DIFFUSION_UNIT) return cen + a.s2 * (dx + dy + dz);   // all scales are exactly 1.0
+        const double ex = dx * a.sx;
+        const double ey = dy * a.sy;
+        const double ez = dz * a.sz;
         return epilogue<LAP_EULER>(ex + ey + ez, cen, cen, a.s1, a.s2, a.gamma);
     };
     // the eight neighbour cells of the patch in the image of level l
