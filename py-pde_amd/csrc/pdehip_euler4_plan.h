@@ -11,7 +11,7 @@ namespace e4plan {
 
 // The tile.  A workgroup owns TY x TZ outputs (rows x fastest axis) and reads (TY + 8) x (TZ + 8) cells of every input plane; a thread owns
 // a patch of PY rows x 2 cells at every level.  Work of the four levels on the shrinking regions: (38*70 + 36*68 + 34*66 + 32*64) / (4 * 32*64)
-// = 1.15 x.  (40 / PY) * (72 / 2) = 720 patches: 768 threads, the last 48 repeat halo patches (patch_of_thread).
+// = 1.15 x.  (40 / PY) * (72 / 2) = 720 patches: 768 threads, 48 of which repeat halo patches (lane_patch).
 constexpr int TY = 32, TZ = 64, PY = 2, LEVELS = 4, HALO = 4;
 constexpr int RY = TY + 2 * HALO, RZ = TZ + 2 * HALO;           // the region of level 0
 constexpr int NPY = RY / PY, NPZ = RZ / 2, PATCHES = NPY * NPZ;
@@ -25,11 +25,45 @@ constexpr int ARR = PATCHES, NARR = LEVELS * PY * 2, GUARD = NPZ;
 constexpr int IMAGE = GUARD + NARR * ARR + GUARD;
 static_assert(PY == 2 && IMAGE <= LEVELS * LROWS * LPITCH, "the image of the four-step sweep fits its LDS allocation");
 
-// The patch of a thread.  The THREADS - PATCHES threads behind the last patch repeat the patch 64 lower - a halo patch, it stores nothing to the
-// field: the same value twice to the same cell of the image, and in every access the lanes of the last wave still touch 64 different
-// consecutive doubles modulo 64 (repeating ONE patch would put a second address on its banks).
+// The row-major numbering of the patches, which is the numbering of the IMAGE (image_index, read_index: patch = py * NPZ + pz), padded to
+// THREADS entries: the THREADS - PATCHES entries behind the last patch repeat the patch 64 lower - a halo patch - so that 64 consecutive
+// entries still touch 64 different consecutive doubles modulo 64.  It was the kernel's lane assignment (thread = patch) and no longer is:
+// the kernel takes a lane's patch from lane_patch below.  tests/test_euler4_image.py enumerates the image through this numbering.
 constexpr int patch_of_thread(int t) { return t < PATCHES ? t : t - 64; }
 static_assert(PATCHES >= 64 && (PATCHES - 64) / NPZ * PY >= HALO + TY, "repeated patches are halo patches");
+
+// The kernel's lane assignment: which patch lane t of the workgroup holds, by the role of its wave.  A patch is needed at as many levels as
+// its distance from the rim of the region allows: the 16 x 32 = 512 output patches at all four, the 100 patches of the ring around them
+// (py = 1, 18 or pz = 1, 34: "ring 1") at levels 1 ... 3, the 108 patches of the outer ring (py = 0, 19 or pz = 0, 35: "ring 0") at level 1
+// alone; 2048 + 300 + 108 = 2456 patch-levels where thread = patch computed 768 * 4 = 3072.  So that whole waves can skip what is not needed:
+//   waves 0 ... 7   the output patches; wave k holds the patch rows 2 + 2k (lanes 0 ... 31: pz = 2 ... 33) and 3 + 2k (lanes 32 ... 63).
+//                   Four levels, and the only waves that store to the field: 512 contiguous bytes per half-wave and row.
+//   wave 8          the four rim columns pz = 0, 1, 34, 35 of the patch rows 2 ... 17, four lanes per row: 32 patches of ring 1, 32 of ring 0.
+//   wave 9          patches 32 ... 71: the end of patch row 0 (pz = 32 ... 35) and patch row 1; 40 lanes.
+//   wave 10         patches 648 ... 687: patch row 18 and the beginning of patch row 19 (pz = 0 ... 3); 40 lanes.
+//                   Waves 8 ... 10 execute levels 1 ... 3.  The other 24 lanes of waves 9 and 10 repeat patches of the OTHER wave of the two
+//                   (the same values to the same cells of the image twice), chosen by their residues - see below.
+//   wave 11         patches 0 ... 31 and 688 ... 719, the rest of ring 0: level 1 only.
+// Waves w, w + 4, w + 8 share a SIMD: three SIMDs execute 4 + 4 + 3 = 11 wave-levels per phase and one 4 + 4 + 1 = 9, 42 instead of 48.
+// Bank conflicts: every access of a lane is base + its patch number, so an 8-byte read (two groups of 32 lanes on 64 banks) is conflict-free
+// when the patches of a half-wave differ modulo 32, and an 8-byte store (four groups of 16 lanes on 32 banks) when those of a quarter-wave
+// differ modulo 16.  Runs of consecutive patches do; NPZ = 36 = 4 (mod 32), so the four rim columns of patch row py have the residues
+// 4 py + 0 ... 3, and eight / four consecutive rows fill a half / quarter of wave 8 exactly; the repeated patches of waves 9 and 10 are runs
+// that complete the residues of their half: 64 ... 71 | 648 ... 671 are 0 ... 7 | 8 ... 31 (mod 32), 680 ... 687 | 64 ... 71 | 48 ... 63 are
+// 8 ... 15 | 0 ... 7 | 16 ... 31.  tests/test_euler4_lanes.py enumerates all of this.
+constexpr int WAVES = THREADS / 64, OWNER_WAVES = 8;
+constexpr int wave_levels(int w) { return w < OWNER_WAVES ? LEVELS : w < WAVES - 1 ? LEVELS - 1 : 1; }   // levels 1 ... wave_levels(w) are executed
+constexpr int lane_patch(int t)
+{
+    const int w = t >> 6, lane = t & 63;
+    if (w < OWNER_WAVES) return (HALO / PY + 2 * w + (lane >> 5)) * NPZ + HALO / 2 + (lane & 31);
+    if (w == 8) return (HALO / PY + (lane >> 2)) * NPZ + ((lane & 2) ? NPZ - 4 : 0) + (lane & 3);   // pz = 0, 1, 34, 35
+    if (w == 9) return lane < 40 ? 32 + lane : 648 + (lane - 40);
+    if (w == 10) return lane < 40 ? 648 + lane : lane < 48 ? 64 + (lane - 40) : lane;
+    return lane < 32 ? lane : PATCHES - 64 + lane;
+}
+static_assert(TY == 32 && TZ == 64 && PY == 2 && HALO == 4 && WAVES == 12, "lane_patch is written for this tile");
+static_assert(OWNER_WAVES * 64 == (TY / PY) * (TZ / 2), "the output patches fill the owner waves exactly");
 
 // index (in doubles) of cell `cell` (0, 1) of row `row` (0 ... PY - 1) of patch `patch` at level `level` (0 ... LEVELS - 1)
 constexpr int image_index(int level, int row, int cell, int patch) { return GUARD + ((level * PY + row) * 2 + cell) * ARR + patch; }

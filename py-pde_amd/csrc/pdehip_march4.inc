@@ -17,8 +17,8 @@
 // The image (e4plan::image_index): per level, patch row and patch cell one array indexed by the patch number, sixteen arrays of 720 doubles
 // between two guard runs of 36, inside the allocation of LEVELS * LROWS * LPITCH doubles.  Every neighbour is a constant offset of the
 // thread's own index (e4plan::read_index): above [row 1][cell][patch - 36], below [row 0][cell][patch + 36], left [row][cell 1][patch - 1],
-// right [row][cell 0][patch + 1].  A wave reads or writes 64 consecutive doubles per access: no bank conflicts, whatever the base
-// (tests/test_euler4_image.py computes the banks).  What a patch at the rim of the region reads - through the row wrap (patch - 1 of a
+// right [row][cell 0][patch + 1].  Every access of a lane is a base plus its patch number, and the patches of a half-wave differ modulo 32,
+// those of a quarter-wave modulo 16: no bank conflicts, whatever the base (tests/test_euler4_lanes.py computes the banks).  What a patch at the rim of the region reads - through the row wrap (patch - 1 of a
 // row's first patch is the last one of the row above), from a neighbouring array or a guard run - is unspecified.  Such a value only ever
 // feeds a cell outside the valid region of its level: level L is valid on the region of level 0 shrunk by L cells per side,
 //     level 0: 40 x 72,   level 1: 38 x 70,   level 2: 36 x 68,   level 3: 34 x 66,   level 4: 32 x 64 (the outputs),
@@ -29,8 +29,17 @@
 // has read that image; then the thread stores its cells of the plane that is the middle plane of level l at the NEXT iteration (level 0:
 // plane i + 2, loaded earlier; level l: what level l - 1 has just computed).  Nothing waits for these stores but the next barrier, so they
 // are under way while the other waves of the SIMD compute; between a store and the read of the same image at the next iteration lie three
-// barriers.  Every thread executes every barrier: halo patches skip the stores to the field, nothing else, and the trip count depends on
-// the workgroup alone.
+// barriers.
+//
+// Waves have roles (e4plan::lane_patch, wave_levels; the lane -> patch map is not the row-major numbering of the image).  A patch is needed at
+// as many levels as its distance from the rim of the region allows - an output patch at all four, the ring around the outputs at levels
+// 1 ... 3, the outer ring at level 1 - and the map gathers the output patches in waves 0 ... 7, the halo patches in waves 8 ... 11, so that a
+// halo wave skips, by scalar branches, the levels none of its patches is needed at: the neighbour reads, the arithmetic and the image stores
+// of those levels (level 0's image stores and the plane loads stay), 42 wave-levels per phase instead of 48 and at most 11 instead of 12 on
+// a SIMD.  Only the owner waves store to the field.  Every wave executes every barrier of every phase - the skips enclose no barrier - and
+// the trip count depends on the workgroup alone.  The cells of a skipped level keep the zeros of the prologue in the image; they are read
+// only by cells that are invalid at their own level, like the unspecified values above (tests/test_euler4_lanes.py enumerates it by lane
+// and by role: whatever a valid cell reads was stored by a wave that executes that level).  The results are the same bits as before.
 //
 // Per cell the arithmetic is `laplace` + `update` of pdehip_march2.inc (cartesian.py:220-227) in the same order: bit-identical to four single
 // steps in the exact build.  One thing is written differently: each `neighbour - 2 * centre` is one fused multiply-add (PDEHIP_E4_MINUS_TWICE:
@@ -45,11 +54,13 @@ __global__ void __launch_bounds__(e4plan::THREADS) euler4_kernel(const LapArgs a
     typedef typename VecT<T, 2>::type V;
     __shared__ __attribute__((aligned(16))) T lds[LEVELS * LROWS * LPITCH];
 
-    // the threads behind the last patch repeat a halo patch (the same values written twice, nothing stored)
-    const int tid = patch_of_thread((int)threadIdx.x);
+    // the lane's patch and the wave's role (e4plan::lane_patch): both wave-uniform values are scalars, so every branch on them is one
+    const int tid = lane_patch((int)threadIdx.x);
+    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    const int nlev = wave_levels(wave);                        // the wave executes levels 1 ... nlev
+    const bool owner = wave < OWNER_WAVES;                     // an owner wave: output patches only, and all of them are in owner waves
     const int py = tid / NPZ, pz = tid - py * NPZ;
     const int ly = py * PY, lz = 2 * pz;                       // first row / column of the patch in the region of level 0
-    const bool owner = ly >= HALO && ly < HALO + TY && lz >= HALO && lz < HALO + TZ;   // (HALO % PY == 0: a patch is output or halo as a whole)
 
     const long w = xcd_swizzle((long)blockIdx.x, a.nblocks);
     const long tiles = a.nty * a.ntz;
@@ -141,22 +152,24 @@ __global__ void __launch_bounds__(e4plan::THREADS) euler4_kernel(const LapArgs a
             const V (&old)[PY] = R[l][(K + 3 - l) % 3];
             const V (&mid)[PY] = R[l][(K + 4 - l) % 3];
             const V (&nw)[PY] = R[l][(K + 5 - l) % 3];
-            T nb[READ_KINDS];
-            fetch(l, nb);
-            if (l < LEVELS - 1) {
-                level(old, mid, nw, nb, R[l + 1][(K + 4 - l) % 3]);
-            } else {
-                V res[PY];
-                level(old, mid, nw, nb, res);
-                const int q = i - 2;   // the local plane of level 4: output plane x0 + q - HALO
-                if (owner && q >= HALO) {
-                    const long po = (x0 + q - HALO) * a.p0;
+            if (l == 0 || l < nlev) {   // level l + 1 is one of the wave's (every wave executes level 1)
+                T nb[READ_KINDS];
+                fetch(l, nb);
+                if (l < LEVELS - 1) {
+                    level(old, mid, nw, nb, R[l + 1][(K + 4 - l) % 3]);
+                } else {                // (owner waves only: nlev == LEVELS)
+                    V res[PY];
+                    level(old, mid, nw, nb, res);
+                    const int q = i - 2;   // the local plane of level 4: output plane x0 + q - HALO
+                    if (owner && q >= HALO) {
+                        const long po = (x0 + q - HALO) * a.p0;
 #pragma unroll
-                    for (int r = 0; r < PY; r++) __builtin_nontemporal_store(res[r], (V *)(out + po + roff[r]));
+                        for (int r = 0; r < PY; r++) __builtin_nontemporal_store(res[r], (V *)(out + po + roff[r]));
+                    }
                 }
             }
             __syncthreads();        // every wave has read the image of level l: the middle plane of the next iteration takes its place
-            store_level(l, nw);
+            if (l <= 1 || l <= nlev) store_level(l, nw);   // (level l >= 1: what the wave has just computed, if it has)
         }
 #pragma unroll
         for (int r = 0; r < PY; r++) R[0][K][r] = pre[r];   // plane i is dead: plane i + 3 takes its slot
