@@ -80,6 +80,45 @@ constexpr int read_index(int level, int kind, int patch)
          : kind < RD_RIGHT0  ? image_index(level, kind - RD_LEFT0, 1, patch - 1)
                              : image_index(level, kind - RD_RIGHT0, 0, patch + 1);
 }
+
+// The second buffers of the images of levels 1 and 2 (two barriers per phase: pdehip_march4.inc).  Each has the shape of a level of the
+// image - a guard run, PY * 2 arrays indexed by the patch number, a guard run - and the two lie one behind the other in an allocation of
+// their own, the kernel's dynamic LDS (ALT_BYTES at the launch); the four images above stay in the static allocation.  alt_index and
+// alt_read_index are image_index and read_index with another base: every access of a lane is again a base plus its patch number, so the
+// residue rule of lane_patch carries over, and a neighbour is the same constant offset of the patch number.  Levels 1 and 2 only.
+constexpr int ALT_LEVELS = 2, ALT_LEVEL = GUARD + PY * 2 * ARR + GUARD;    // buffers; doubles per buffer
+constexpr int ALT_IMAGE = ALT_LEVELS * ALT_LEVEL;
+constexpr long ALT_BYTES = (long)ALT_IMAGE * 8;
+constexpr int alt_index(int level, int row, int cell, int patch) { return (level - 1) * ALT_LEVEL + GUARD + (row * 2 + cell) * ARR + patch; }
+constexpr int alt_read_index(int level, int kind, int patch)
+{
+    return kind < RD_BELOW0  ? alt_index(level, PY - 1, kind - RD_ABOVE0, patch - NPZ)
+         : kind < RD_LEFT0   ? alt_index(level, 0, kind - RD_BELOW0, patch + NPZ)
+         : kind < RD_RIGHT0  ? alt_index(level, kind - RD_LEFT0, 1, patch - 1)
+                             : alt_index(level, kind - RD_RIGHT0, 0, patch + 1);
+}
+static_assert(LDS_BYTES % 16 == 0 && ALT_BYTES % 16 == 0 && LDS_BYTES + ALT_BYTES <= 160 * 1024, "static and dynamic LDS of the four-step sweep");
+
+// The order of a phase of pdehip_march4.inc, which the kernel follows and tests/test_euler4_double_buffer.py replays: what a wave does to
+// which image between which barriers.  `other`: 0 = the buffer of the phase's parity p (images 0 and 3 have one buffer: always 0),
+// 1 = the buffer 1 - p.  `interval`: 0 = between barrier B of the phase before (the prologue's barrier) and A, 1 = between A and B.
+// Waves run freely inside an interval, so a store and a read of one buffer are ordered if and only if they lie in different intervals.
+enum SchedOp { SCH_STORE, SCH_READ, SCH_BARRIER };
+struct SchedEvent { int op, image, other, interval; };
+constexpr SchedEvent SCHEDULE[] = {
+    {SCH_STORE, 3, 0, 0},     // level 3's middle plane of this phase, computed in the phase before
+    {SCH_READ, 0, 0, 0},      // l = 0: level 1 ...
+    {SCH_STORE, 1, 1, 0},     // ... into the other buffer of image 1
+    {SCH_BARRIER, -1, 0, 0},  // A: every wave has read image 0
+    {SCH_STORE, 0, 0, 1},     // plane i + 2
+    {SCH_READ, 1, 0, 1},      // l = 1: level 2 ...
+    {SCH_STORE, 2, 1, 1},     // ... into the other buffer of image 2
+    {SCH_READ, 2, 0, 1},      // l = 2: level 3, kept in registers
+    {SCH_READ, 3, 0, 1},      // l = 3: level 4, to the field
+    {SCH_BARRIER, -1, 0, 1},  // B: every wave has read image 3
+};
+constexpr int SCHEDULE_EVENTS = sizeof(SCHEDULE) / sizeof(SCHEDULE[0]);
+
 // x - 2 * c in ONE instruction.  The reference computes vm = 2 * c and then x - vm (cartesian.py:220-227): two roundings on paper, but doubling
 // is exact, so x - vm is the real number x - 2c rounded once - which is what the fused multiply-add returns.  Bit for bit the same for all
 // finite c up to half the largest double (beyond it 2 * c overflows to infinity and the fused form does not; tests/test_euler4_fma.py walks

@@ -50,16 +50,24 @@ int launch_euler4(const NGrid &n, const void *in, void *out, double s1, double s
     e4plan::format_name(c, name, sizeof(name));
     note_kernel("%s", name);
     void *args[] = {&a};
-    PDEHIP_HIP(hipLaunchKernel(kernel, dim3((unsigned)c.nblocks), dim3(c.block), args, 0, st));
+    // dynamic LDS: the second buffers of images 1 and 2 (preload_e4_kernels has asked for the size; a captured launch carries it in its node)
+    PDEHIP_HIP(hipLaunchKernel(kernel, dim3((unsigned)c.nblocks), dim3(c.block), args, (size_t)e4plan::ALT_BYTES, st));
     *done = true;
     return 0;
 }
 
 // (the code object of this translation unit is loaded when the device is selected, not in the middle of a run: preload_stencil_kernels)
+// Both instances are told how much dynamic LDS their launches ask for.  A runtime that refuses the size fails the device selection with its
+// error, and one that refuses it at the launch fails the run: there is no other version of this kernel.
 int preload_e4_kernels()
 {
-    hipFuncAttributes attr;
-    PDEHIP_HIP(hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(&euler4_kernel<double, E2_DIFFUSION_UNIT>)));
+    const void *const kernels[] = {reinterpret_cast<const void *>(&euler4_kernel<double, E2_DIFFUSION_UNIT>),
+                                   reinterpret_cast<const void *>(&euler4_kernel<double, E2_DIFFUSION>)};
+    for (const void *kernel : kernels) {
+        PDEHIP_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e4plan::ALT_BYTES));
+        hipFuncAttributes attr;
+        PDEHIP_HIP(hipFuncGetAttributes(&attr, kernel));
+    }
     return 0;
 }
 

@@ -25,11 +25,27 @@
 // a cell that is valid at level L has all four in-plane neighbours inside the region of level L - 1, and those are read where their owners
 // stored them (the same test enumerates it).  The guard runs are zeroed once so that whole images compare equal; no result depends on it.
 //
-// A phase (one iteration) has one barrier per level: the arithmetic of level l, which reads the image of level l; a barrier - every wave
-// has read that image; then the thread stores its cells of the plane that is the middle plane of level l at the NEXT iteration (level 0:
-// plane i + 2, loaded earlier; level l: what level l - 1 has just computed).  Nothing waits for these stores but the next barrier, so they
-// are under way while the other waves of the SIMD compute; between a store and the read of the same image at the next iteration lie three
-// barriers.
+// A phase (one iteration) has two barriers, A and B (e4plan::SCHEDULE is this order as a table; tests/test_euler4_double_buffer.py replays
+// it).  Image l holds the middle plane of level l; level l + 1 reads it in every phase and the middle plane of the NEXT iteration must take
+// its place (level 0: plane i + 2, loaded earlier; level l: what level l - 1 computes in this phase).  A barrier per image guarded that
+// overwrite against the reads and brought the waves into step four times per phase.  Now the images of levels 1 and 2 have a second buffer
+// (e4plan::alt_index; dynamic LDS, an object of its own) and the two change places from phase to phase, p = the parity of the iteration:
+//     store image 3               level 3's middle plane, computed by l = 2 of the phase before and still in its registers
+//     l = 0: read image 0, level 1;   store image 1[1 - p]
+//     barrier A                   every wave has read image 0
+//     store image 0               plane i + 2
+//     l = 1: read image 1[p], level 2;   store image 2[1 - p]
+//     l = 2: read image 2[p], level 3    (stays in registers until B has passed)
+//     l = 3: read image 3, level 4 -> the field (owner waves)
+//     barrier B                   every wave has read image 3
+// Waves run freely between two barriers, so a store and a read of one buffer are ordered exactly when a barrier lies between them:
+//   * buffers 1[1 - p] and 2[1 - p] were last read in the phase before, ahead of its B, and are next read in the next phase, behind this B
+//     (and its A);
+//   * image 0 is read before A and written behind it; its next read lies behind B;
+//   * image 3 is read before B and written behind it; its next read lies behind A of the next phase.
+// The stores of levels 1 and 2 are issued where their data is produced and nothing waits for them but the next barrier.  The buffer bases
+// are wave-uniform (scalar registers, swapped after B); a lane adds its patch number to them.  The prologue stores the middle planes of
+// iteration 0 (parity 0) into the buffers 0 and zeroes the second buffers with their guard runs, behind one barrier.
 //
 // Waves have roles (e4plan::lane_patch, wave_levels; the lane -> patch map is not the row-major numbering of the image).  A patch is needed at
 // as many levels as its distance from the rim of the region allows - an output patch at all four, the ring around the outputs at levels
@@ -53,6 +69,9 @@ __global__ void __launch_bounds__(e4plan::THREADS) euler4_kernel(const LapArgs a
     using namespace e4plan;
     typedef typename VecT<T, 2>::type V;
     __shared__ __attribute__((aligned(16))) T lds[LEVELS * LROWS * LPITCH];
+    // the second buffers of images 1 and 2 (ALT_BYTES of dynamic LDS): an object of its own, wherever it lies relative to `lds`
+    extern __shared__ __attribute__((aligned(16))) unsigned char euler4_alt[];
+    typedef __attribute__((address_space(3))) T LT;
 
     // the lane's patch and the wave's role (e4plan::lane_patch): both wave-uniform values are scalars, so every branch on them is one
     const int tid = lane_patch((int)threadIdx.x);
@@ -90,6 +109,13 @@ __global__ void __launch_bounds__(e4plan::THREADS) euler4_kernel(const LapArgs a
     int me2 = tid;
     asm volatile("" : "+v"(me2));
     if ((int)threadIdx.x < GUARD) lds[threadIdx.x] = lds[IMAGE - GUARD + threadIdx.x] = 0;   // (no result depends on it)
+    // The two buffers of image l = 1, 2 as bases that alt_index / alt_read_index are added to: cur[l - 1] is read in this phase, oth[l - 1]
+    // written; they change places after every phase (wave-uniform values: scalar moves, and one add per index register and phase).
+    // Buffer 0 is the level's part of `lds`, buffer 1 lies in the dynamic array.
+    LT *const alt = (LT *)euler4_alt;
+    LT *cur[ALT_LEVELS] = {(LT *)lds + (image_index(1, 0, 0, 0) - alt_index(1, 0, 0, 0)), (LT *)lds + (image_index(2, 0, 0, 0) - alt_index(2, 0, 0, 0))};
+    LT *oth[ALT_LEVELS] = {alt, alt};
+    for (int k = (int)threadIdx.x; k < ALT_IMAGE; k += THREADS) alt[k] = 0;   // arrays and guard runs: a skipped level's cells stay zero
 
     auto update = [&](double xm, double xp, double up, double dn, double left, double right, double cen) {
         // (xm - 2 * cen) + xp and so on, as the reference rounds them
@@ -127,6 +153,24 @@ __global__ void __launch_bounds__(e4plan::THREADS) euler4_kernel(const LapArgs a
         }
     };
 
+    // the same for images 1 and 2, in the buffer at `base` (cur or oth)
+    auto fetch_alt = [&](int l, LT *base, T (&nb)[READ_KINDS]) {
+        LT *const b = base + me, *const b2 = base + me2;
+#pragma unroll
+        for (int k = 0; k < READ_KINDS; k++) {
+            const bool second = k == RD_BELOW1 || k == RD_LEFT1 || k == RD_RIGHT0 || k == RD_RIGHT1;
+            nb[k] = (second ? b2 : b)[alt_read_index(l, k, 0)];
+        }
+    };
+    auto store_alt = [&](int l, LT *base, const V (&pl)[PY]) {
+        LT *const b = base + me;
+#pragma unroll
+        for (int r = 0; r < PY; r++) {
+            b[alt_index(l, r, 0, 0)] = pl[r][0];
+            b[alt_index(l, r, 1, 0)] = pl[r][1];
+        }
+    };
+
     // R[L][s]: level L, plane slot s; slot of local plane j = j mod 3
     V R[LEVELS][3][PY], pre[PY];
 #pragma unroll
@@ -142,10 +186,13 @@ __global__ void __launch_bounds__(e4plan::THREADS) euler4_kernel(const LapArgs a
     for (int l = 0; l < LEVELS; l++) store_level(l, R[l][(4 - l) % 3]);   // the middle planes of iteration 0 (level 0: plane 1; the others: zeros)
     __syncthreads();
 
-    // iteration i, i mod 3 == K: level 0 holds planes i, i + 1, i + 2 in slots K, K + 1, K + 2 (mod 3); level L the planes L lower
+    // iteration i, i mod 3 == K: level 0 holds planes i, i + 1, i + 2 in slots K, K + 1, K + 2 (mod 3); level L the planes L lower.
+    // The order of the LDS traffic and the two barriers is e4plan::SCHEDULE.
     auto phase = [&](int i, auto kc) {
         constexpr int K = decltype(kc)::value;
         load_plane(i + 3, pre);   // needed at the next iteration
+        // level 3's middle plane of THIS iteration, computed by l = 2 of the one before (iteration 0: the prologue's zeros once more)
+        if (LEVELS - 1 <= nlev) store_level(LEVELS - 1, R[LEVELS - 1][(K + 1) % 3]);
 #pragma unroll
         for (int l = 0; l < LEVELS; l++) {
             // level l holds planes (i - l, i + 1 - l, i + 2 - l); level l + 1 gets plane i + 1 - l, in the slot of its plane i - 2 - l
@@ -154,9 +201,14 @@ __global__ void __launch_bounds__(e4plan::THREADS) euler4_kernel(const LapArgs a
             const V (&nw)[PY] = R[l][(K + 5 - l) % 3];
             if (l == 0 || l < nlev) {   // level l + 1 is one of the wave's (every wave executes level 1)
                 T nb[READ_KINDS];
-                fetch(l, nb);
+                if (l == 0 || l == LEVELS - 1) fetch(l, nb);
+                else fetch_alt(l, cur[l - 1], nb);
                 if (l < LEVELS - 1) {
-                    level(old, mid, nw, nb, R[l + 1][(K + 4 - l) % 3]);
+                    V (&res)[PY] = R[l + 1][(K + 4 - l) % 3];
+                    level(old, mid, nw, nb, res);
+                    // the middle plane of level l + 1 at the next iteration, into the buffer nobody reads in this phase (level 3: kept in
+                    // its registers until barrier B has passed)
+                    if (l + 1 < LEVELS - 1) store_alt(l + 1, oth[l], res);
                 } else {                // (owner waves only: nlev == LEVELS)
                     V res[PY];
                     level(old, mid, nw, nb, res);
@@ -168,11 +220,20 @@ __global__ void __launch_bounds__(e4plan::THREADS) euler4_kernel(const LapArgs a
                     }
                 }
             }
-            __syncthreads();        // every wave has read the image of level l: the middle plane of the next iteration takes its place
-            if (l <= 1 || l <= nlev) store_level(l, nw);   // (level l >= 1: what the wave has just computed, if it has)
+            if (l == 0) {
+                __syncthreads();        // A: every wave has read the image of level 0 ...
+                store_level(0, nw);     // ... plane i + 2 takes its place
+            }
         }
+        __syncthreads();                // B: every wave has read the image of level 3 (and the buffers `cur` of levels 1 and 2)
 #pragma unroll
         for (int r = 0; r < PY; r++) R[0][K][r] = pre[r];   // plane i is dead: plane i + 3 takes its slot
+#pragma unroll
+        for (int b = 0; b < ALT_LEVELS; b++) {
+            LT *const t = cur[b];
+            cur[b] = oth[b];
+            oth[b] = t;
+        }
     };
     const int iend = lx + 2 * HALO - 3;   // the last iteration: level 4 at plane lx + HALO - 1
     for (int i = 0;; i += 3) {
