@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "pdehip_common.h"
+#include "pdehip_scratch.h"
 #include "pdehip_slab_loops.h"
 #include "pdehip_block_loops.h"
 
@@ -493,7 +494,18 @@ int check_rhs(const pdehip_rhs_t *rhs)
     return 0;
 }
 
+// what pdehip_release_scratch frees beside the buffers of the serial context (register_scratch_release, pdehip_scratch.h).  The list is
+// a static of this function, so that the tables of other units can add themselves whatever the order in which the library's statics are
+// initialised
+std::vector<int (*)()> &scratch_releases()
+{
+    static std::vector<int (*)()> list;
+    return list;
+}
+
 }  // namespace
+
+void pdehip::register_scratch_release(int (*release)()) { scratch_releases().push_back(release); }
 
 extern "C" {
 
@@ -542,12 +554,12 @@ int pdehip_comm_destroy(void *comm)
 int pdehip_release_scratch(void)
 {
     release_scratch(serial_context());
-    const int rc = stats_release_scratch();
-    const int rc2 = project_release_scratch();
-    const int rc3 = smooth_release_scratch();
-    const int rc4 = hist_release_scratch();
-    const int rc5 = label_release_scratch();
-    return rc ? rc : (rc2 ? rc2 : (rc3 ? rc3 : (rc4 ? rc4 : rc5)));
+    int rc = 0;
+    for (int (*release)() : scratch_releases()) {      // the per-stream tables of the analysis kernels (pdehip_scratch.h)
+        const int r = release();
+        if (!rc) rc = r;
+    }
+    return rc;
 }
 
 // what RCCL itself says about the communicator: out5 = {ncclCommCount, ncclCommUserRank, ncclCommCuDevice, ncclGetVersion, HIP device of the

@@ -154,11 +154,6 @@ struct Euler2Plan {
     bool has_y;
 };
 int preload_shell_kernels();     // pdehip_shell.hip: the same for its code object
-int stats_release_scratch();     // pdehip_stats.hip: frees the per-stream slots of its sweeps (pdehip_release_scratch)
-int project_release_scratch();   // pdehip_project.hip: the same for the partial results of its stages
-int smooth_release_scratch();    // pdehip_smooth.hip: the same for the staged weights of its passes
-int hist_release_scratch();      // pdehip_hist.hip: the same for the partial histograms, staged edges and control blocks
-int label_release_scratch();     // pdehip_label.hip: the same for the parent array, the chunk counts of the scan and the counter of refused labels
 #include "pdehip_launchers.h"
 namespace exactv {
 #include "pdehip_launchers.h"

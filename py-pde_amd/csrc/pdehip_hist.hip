@@ -7,11 +7,9 @@
 // 32-bit counters in LDS; lanes of a wave that hit the same counter are combined before the LDS add (a two-phase field puts nearly every
 // cell in two bins, a field of equal values puts every digit of the selection in one bucket).  Compiled without FMA contraction in every
 // build, like the statistics (the norm over the components is evaluated the same way).
-#include <map>
-#include <mutex>
-
 #include "pdehip_common.h"
 #include "pdehip_pieces.h"
+#include "pdehip_scratch.h"
 #include "pdehip_sweep.h"
 
 namespace pdehip {
@@ -26,9 +24,7 @@ constexpr int kSelectDigits = 256;                   // 8-bit digits: 8 sweeps f
 // and lower still where a workgroup has thousands of counters; 2048 workgroups are 8 waves per SIMD on 256 CUs.
 inline unsigned hist_blocks(long pieces, int counters)
 {
-    const long cap = counters > 1024 ? 768 : 2048;
-    const long b = (pieces + 255) / 256;
-    return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
+    return blocks_for(pieces, counters > 1024 ? 768 : 2048);
 }
 
 // One more cell for counter `slot` (lanes with !active only take part in the votes).  Two rounds in which the lanes that share the slot
@@ -51,33 +47,6 @@ __device__ __forceinline__ void lds_count(unsigned *cnt, int slot, bool active)
         }
     }
     if (active) atomicAdd(&cnt[slot], 1u);
-}
-
-// The row loop of for_row_pieces<VEC> (pdehip_sweep.h) with the loads of kAhead pieces issued before the first of them is used: what is
-// done per cell here (a search, votes, LDS adds) is long enough to leave the memory idle behind a single load per thread.
-// load(element, values) fills the values of a piece, use(values) consumes them; the order per thread is fixed.
-constexpr int kAhead = 4;
-template <typename T, int VEC, class L, class U>
-__device__ __forceinline__ void for_row_pieces_ahead(const RowGrid &g, L &&load, U &&use)
-{
-    const long per_row = g.n2 / VEC;
-    const long total = g.n0 * g.n1 * per_row;
-    const long stride = (long)gridDim.x * blockDim.x;
-    for (long t = blockIdx.x * (long)blockDim.x + threadIdx.x; t < total; t += kAhead * stride) {
-        T v[kAhead][VEC];
-#pragma unroll
-        for (int u = 0; u < kAhead; u++) {
-            const long tu = t + u * stride < total ? t + u * stride : t;      // (past the end: the first piece once more, not used)
-            long rest = tu;
-            const long k = (rest % per_row) * VEC; rest /= per_row;
-            const long j = rest % g.n1;
-            const long i = rest / g.n1;
-            load(g.off + i * g.p0 + j * g.p1 + k, v[u]);
-        }
-#pragma unroll
-        for (int u = 0; u < kAhead; u++)
-            if (t + u * stride < total) use(v[u]);
-    }
 }
 
 // ---- histogram --------------------------------------------------------------------------------------------------------------------------
@@ -326,64 +295,51 @@ __global__ void __launch_bounds__(256) select_scan_kernel(SelectCtl *ctls, int p
 // ---- per stream: pinned host memory for the edges of a call (they are checked on the host) and the control blocks of the selection;
 // allocated at the stream's first call, kept until pdehip_release_scratch -------------------------------------------------------------------
 struct HistScratch { double *edges_host; SelectCtl *ctl; };
-std::mutex g_mu;
-std::map<hipStream_t, HistScratch> g_table;
+int release_blocks();
+StreamTable<HistScratch> g_table(release_blocks);
+
+int release_blocks()
+{
+    return g_table.release([](HistScratch &h) {
+        (void)hipFree(h.ctl);                  // (hipFree waits for the device: no pass still uses the control blocks)
+        (void)hipHostFree(h.edges_host);
+    });
+}
 
 int hist_scratch(hipStream_t st, HistScratch *s)
 {
-    std::lock_guard<std::mutex> lock(g_mu);
-    auto it = g_table.find(st);
-    if (it == g_table.end()) {
-        HistScratch h{nullptr, nullptr};
-        PDEHIP_HIP(hipHostMalloc((void **)&h.edges_host, sizeof(double) * (kHistBinsMax + 1), hipHostMallocDefault));
-        const hipError_t e = hipMalloc((void **)&h.ctl, sizeof(SelectCtl) * 64);
-        if (e != hipSuccess) {
-            (void)hipHostFree(h.edges_host);
-            PDEHIP_FAIL(100 + (int)e, "hipMalloc of the selection's control blocks failed: %s", hipGetErrorString(e));
+    return g_table.with(st, [&](HistScratch &h) -> int {
+        if (!h.ctl) {
+            PDEHIP_HIP(hipHostMalloc((void **)&h.edges_host, sizeof(double) * (kHistBinsMax + 1), hipHostMallocDefault));
+            const hipError_t e = hipMalloc((void **)&h.ctl, sizeof(SelectCtl) * 64);
+            if (e != hipSuccess) {
+                (void)hipHostFree(h.edges_host);
+                h.edges_host = nullptr; h.ctl = nullptr;
+                PDEHIP_FAIL(100 + (int)e, "hipMalloc of the selection's control blocks failed: %s", hipGetErrorString(e));
+            }
         }
-        it = g_table.emplace(st, h).first;
-    }
-    *s = it->second;
-    return 0;
+        *s = h;
+        return 0;
+    });
 }
 
 template <bool NORM, bool UNIFORM>
 void launch_hist(const NGrid &n, int vec, dim3 grid, size_t lds, hipStream_t st, const HistArgs &a)
 {
-#define PDEHIP_HIST(T, V) hipLaunchKernelGGL((hist_sweep_kernel<T, V, NORM, UNIFORM>), grid, dim3(256), lds, st, a)
-    if (n.dtype == PDEHIP_F64) {
-        if (vec == 2) PDEHIP_HIST(double, 2); else PDEHIP_HIST(double, 1);
-    } else {
-        if (vec == 4) PDEHIP_HIST(float, 4); else PDEHIP_HIST(float, 1);
-    }
-#undef PDEHIP_HIST
+    dispatch_piece(n.dtype, vec, [&](auto type, auto width) {
+        hipLaunchKernelGGL((hist_sweep_kernel<decltype(type), decltype(width)::value, NORM, UNIFORM>), grid, dim3(256), lds, st, a);
+    });
 }
 
 template <bool NORM>
 void launch_select(const NGrid &n, int vec, dim3 grid, hipStream_t st, const SelectArgs &a)
 {
-#define PDEHIP_SELECT(T, V) hipLaunchKernelGGL((select_sweep_kernel<T, V, NORM>), grid, dim3(256), 0, st, a)
-    if (n.dtype == PDEHIP_F64) {
-        if (vec == 2) PDEHIP_SELECT(double, 2); else PDEHIP_SELECT(double, 1);
-    } else {
-        if (vec == 4) PDEHIP_SELECT(float, 4); else PDEHIP_SELECT(float, 1);
-    }
-#undef PDEHIP_SELECT
+    dispatch_piece(n.dtype, vec, [&](auto type, auto width) {
+        hipLaunchKernelGGL((select_sweep_kernel<decltype(type), decltype(width)::value, NORM>), grid, dim3(256), 0, st, a);
+    });
 }
 
 }  // namespace
-
-int hist_release_scratch()
-{
-    std::lock_guard<std::mutex> lock(g_mu);
-    for (auto &e : g_table) {
-        (void)hipFree(e.second.ctl);           // (hipFree waits for the device: no pass still uses the control blocks)
-        (void)hipHostFree(e.second.edges_host);
-    }
-    g_table.clear();
-    return 0;
-}
-
 }  // namespace pdehip
 
 using namespace pdehip;

@@ -15,10 +15,8 @@
 //   (e) domain_sizes_kernel integer adds; the lanes of a wave that hit the same label are combined, and a wave keeps the label it met
 //                           last in a register (one percolating domain costs one add per wave, not one per cell)
 // Everything is integer work: the result does not depend on the order in which workgroups run.  No kernel waits for another workgroup.
-#include <map>
-#include <mutex>
-
 #include "pdehip_common.h"
+#include "pdehip_scratch.h"
 
 namespace pdehip {
 namespace {
@@ -292,52 +290,48 @@ struct LabelScratch {
     long chunk_slots;
     unsigned long long *bad_dev, *bad_host;
 };
-std::mutex g_mu;
-std::map<hipStream_t, LabelScratch> g_table;
+int release_arrays();
+StreamTable<LabelScratch> g_table(release_arrays);
+
+int release_arrays()
+{
+    return g_table.release([](LabelScratch &s) {
+        if (s.parent) (void)hipFree(s.parent);
+        if (s.chunks) (void)hipFree(s.chunks);
+        if (s.bad_dev) (void)hipFree(s.bad_dev);
+        if (s.bad_host) (void)hipHostFree(s.bad_host);
+    });
+}
 
 int label_scratch(hipStream_t st, long cells, LabelScratch *out)
 {
-    std::lock_guard<std::mutex> lock(g_mu);
-    LabelScratch &s = g_table[st];          // (a new entry is all zeros)
-    if (!s.bad_dev) {
-        PDEHIP_HIP(hipMalloc((void **)&s.bad_dev, 16));
-        PDEHIP_HIP(hipHostMalloc((void **)&s.bad_host, 16, hipHostMallocDefault));
-    }
-    if (cells > s.parent_cells) {
-        // (hipFree waits for the device: no launch still uses the smaller arrays)
-        if (s.parent) (void)hipFree(s.parent);
-        if (s.chunks) (void)hipFree(s.chunks);
-        s.parent = nullptr; s.chunks = nullptr; s.parent_cells = 0; s.chunk_slots = 0;
-        const long slots = (cells + kChunk - 1) / kChunk;
-        PDEHIP_HIP(hipMalloc((void **)&s.parent, sizeof(int) * (size_t)cells));
-        const hipError_t e = hipMalloc((void **)&s.chunks, sizeof(unsigned) * 2 * (size_t)slots);
-        if (e != hipSuccess) {
-            (void)hipFree(s.parent);
-            s.parent = nullptr;
-            PDEHIP_FAIL(100 + (int)e, "hipMalloc of the labelling's chunk counts failed: %s", hipGetErrorString(e));
+    return g_table.with(st, [&](LabelScratch &s) -> int {      // (a new entry is all zeros)
+        if (!s.bad_dev) {
+            PDEHIP_HIP(hipMalloc((void **)&s.bad_dev, 16));
+            PDEHIP_HIP(hipHostMalloc((void **)&s.bad_host, 16, hipHostMallocDefault));
         }
-        s.parent_cells = cells;
-        s.chunk_slots = slots;
-    }
-    *out = s;
-    return 0;
+        if (cells > s.parent_cells) {
+            // (hipFree waits for the device: no launch still uses the smaller arrays)
+            if (s.parent) (void)hipFree(s.parent);
+            if (s.chunks) (void)hipFree(s.chunks);
+            s.parent = nullptr; s.chunks = nullptr; s.parent_cells = 0; s.chunk_slots = 0;
+            const long slots = (cells + kChunk - 1) / kChunk;
+            PDEHIP_HIP(hipMalloc((void **)&s.parent, sizeof(int) * (size_t)cells));
+            const hipError_t e = hipMalloc((void **)&s.chunks, sizeof(unsigned) * 2 * (size_t)slots);
+            if (e != hipSuccess) {
+                (void)hipFree(s.parent);
+                s.parent = nullptr;
+                PDEHIP_FAIL(100 + (int)e, "hipMalloc of the labelling's chunk counts failed: %s", hipGetErrorString(e));
+            }
+            s.parent_cells = cells;
+            s.chunk_slots = slots;
+        }
+        *out = s;
+        return 0;
+    });
 }
 
 }  // namespace
-
-int label_release_scratch()
-{
-    std::lock_guard<std::mutex> lock(g_mu);
-    for (auto &e : g_table) {
-        if (e.second.parent) (void)hipFree(e.second.parent);
-        if (e.second.chunks) (void)hipFree(e.second.chunks);
-        if (e.second.bad_dev) (void)hipFree(e.second.bad_dev);
-        if (e.second.bad_host) (void)hipHostFree(e.second.bad_host);
-    }
-    g_table.clear();
-    return 0;
-}
-
 }  // namespace pdehip
 
 using namespace pdehip;

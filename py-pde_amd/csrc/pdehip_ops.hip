@@ -2,9 +2,7 @@
 // pointwise kernels of the Runge–Kutta steppers (all bandwidth-bound, 16-byte vector access
 // over the interior rows of the aligned device layout).
 #include "pdehip_common.h"
-
-#include <map>
-#include <mutex>
+#include "pdehip_scratch.h"
 
 namespace pdehip {
 
@@ -227,17 +225,12 @@ __global__ void __launch_bounds__(256) final_sum_kernel(SumArgs a)
 constexpr int kSumBlocks = 1024;
 static int sum_scratch(hipStream_t st, double **partial)
 {
-    static std::mutex mu;
-    static std::map<hipStream_t, double *> table;
-    std::lock_guard<std::mutex> lock(mu);
-    auto it = table.find(st);
-    if (it == table.end()) {
-        double *p = nullptr;
-        PDEHIP_HIP(hipMalloc(&p, sizeof(double) * 64 * kSumBlocks));
-        it = table.emplace(st, p).first;
-    }
-    *partial = it->second;
-    return 0;
+    static StreamTable<double *> table;      // (not registered: kept for the process, see above)
+    return table.with(st, [&](double *&p) -> int {
+        if (!p) PDEHIP_HIP(hipMalloc(&p, sizeof(double) * 64 * kSumBlocks));
+        *partial = p;
+        return 0;
+    });
 }
 
 // ---- Gaussian white noise increment of an Euler-Maruyama step (pde/solvers/euler.py:66-147) -----------------------------

@@ -1,6 +1,10 @@
-// pdehip_pieces.h — what the sweeps that only READ a field share (pdehip_stats.hip, pdehip_hist.hip): VEC cells of a row in one access,
-// and the values of such a piece - the cells of one component, or the norm over the components.
+// pdehip_pieces.h — VEC cells of a row in one access, for the analysis kernels: the loader (pdehip_stats.hip, pdehip_hist.hip,
+// pdehip_project.hip, pdehip_smooth.hip) and the store (pdehip_stats.hip), the values of such a piece - the cells of one component, or
+// the norm over the components (pdehip_stats.hip, pdehip_hist.hip) - and, on the host, the one rule for VEC (piece_width) and the one
+// choice of the kernel instance <type, VEC> (dispatch_piece), which all four units use.
 #pragma once
+
+#include <type_traits>
 
 #include "pdehip_common.h"
 
@@ -60,6 +64,18 @@ inline int piece_width(const NGrid &n, const void *a, const void *b)
     if ((((uintptr_t)a | (uintptr_t)b) & 15) != 0) return 1;
     if (n.dtype == PDEHIP_F64) return n.n[2] % 2 == 0 ? 2 : 1;
     return n.n[2] % 4 == 0 ? 4 : 1;
+}
+
+// fn(T(), std::integral_constant<int, VEC>()) for the one of <double, 2>, <double, 1>, <float, 4>, <float, 1> that `dtype` and the width
+// of piece_width name: the caller's generic lambda launches its kernel instance <T, VEC>
+template <class F>
+inline void dispatch_piece(int dtype, int vec, F &&fn)
+{
+    if (dtype == PDEHIP_F64) {
+        if (vec == 2) fn(double(), std::integral_constant<int, 2>()); else fn(double(), std::integral_constant<int, 1>());
+    } else {
+        if (vec == 4) fn(float(), std::integral_constant<int, 4>()); else fn(float(), std::integral_constant<int, 1>());
+    }
 }
 
 }  // namespace pdehip

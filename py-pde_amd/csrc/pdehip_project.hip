@@ -16,10 +16,9 @@
 // Every thread's order is fixed by the launch geometry and no atomics are used: two calls give equal bits.  A term of a sum is
 // (double)x * weight, one rounding; every addition is one rounding (compiled without FMA contraction in every build).  The maximum
 // keeps a NaN once it met one (np.max); the minimum is -max(-x), both negations exact.
-#include <map>
-#include <mutex>
-
 #include "pdehip_common.h"
+#include "pdehip_pieces.h"
+#include "pdehip_scratch.h"
 #include "pdehip_sweep.h"
 
 namespace pdehip {
@@ -27,19 +26,6 @@ namespace {
 
 constexpr long kProjectSegment = 128;      // removed cells one thread of the march marches over (tests/project_cases.py: SEGMENT)
 constexpr long kProjectBlocksMax = 1024;   // workgroups of a launch; what is beyond takes a grid-stride turn (tests/project_cases.py: TURN_THREADS)
-
-template <typename T, int VEC>
-__device__ __forceinline__ void load_cells(const T *p, T (&v)[VEC])
-{
-    if constexpr (VEC == 1) {
-        v[0] = p[0];
-    } else {
-        typedef T vec_t __attribute__((ext_vector_type(VEC)));
-        const vec_t x = *(const vec_t *)p;
-#pragma unroll
-        for (int q = 0; q < VEC; q++) v[q] = x[q];
-    }
-}
 
 struct OpSum {
     __device__ static double identity() { return 0.0; }
@@ -100,13 +86,13 @@ __global__ void __launch_bounds__(256) project_row_kernel(ProjectArgs a)
             for (; c + 3L * gw < per_row; c += 4L * gw) {
                 T v[4][VEC];
 #pragma unroll
-                for (int u = 0; u < 4; u++) load_cells<T, VEC>(p + (c + (long)u * gw) * VEC, v[u]);
+                for (int u = 0; u < 4; u++) load_piece<T, VEC>(p + (c + (long)u * gw) * VEC, v[u]);
 #pragma unroll
                 for (int u = 0; u < 4; u++) take<OP, T, VEC>(acc, v[u], a.weight);
             }
             for (; c < per_row; c += gw) {
                 T v[VEC];
-                load_cells<T, VEC>(p + c * VEC, v);
+                load_piece<T, VEC>(p + c * VEC, v);
                 take<OP, T, VEC>(acc, v, a.weight);
             }
         }
@@ -138,7 +124,7 @@ __global__ void __launch_bounds__(256) project_march_kernel(ProjectArgs a)
             T v[4][VEC];
 #pragma unroll
             for (int u = 0; u < 4; u++) {
-                load_cells<T, VEC>(p, v[u]);
+                load_piece<T, VEC>(p, v[u]);
                 p += a.g.p1;
                 if (++j == a.m1) { j = 0; p += wrap; }
             }
@@ -149,7 +135,7 @@ __global__ void __launch_bounds__(256) project_march_kernel(ProjectArgs a)
         }
         for (; r < end; r++) {
             T v[VEC];
-            load_cells<T, VEC>(p, v);
+            load_piece<T, VEC>(p, v);
             p += a.g.p1;
             if (++j == a.m1) { j = 0; p += wrap; }
 #pragma unroll
@@ -186,27 +172,26 @@ __global__ void __launch_bounds__(256) extract_box_kernel(BoxArgs a)
 // ---- the partial results of the stages: two halves used in turn, one buffer per STREAM (calls on one stream are ordered; two streams
 // reducing at the same time must not share one), grown on demand and kept until pdehip_release_scratch ---------------------------------
 struct ProjectScratch { double *p; size_t doubles; };
-std::mutex g_mu;
-std::map<hipStream_t, ProjectScratch> g_table;
+int release_partials();
+StreamTable<ProjectScratch> g_table(release_partials);
+
+int release_partials()
+{
+    return g_table.release([](ProjectScratch &s) { (void)hipFree(s.p); });
+}
 
 int project_scratch(hipStream_t st, size_t doubles, double **p)
 {
-    std::lock_guard<std::mutex> lock(g_mu);
-    ProjectScratch &s = g_table[st];
-    if (s.doubles < doubles) {
-        if (s.p) (void)hipFree(s.p);       // (hipFree waits for the device: no stage still reads the old buffer)
-        s.p = nullptr; s.doubles = 0;
-        PDEHIP_HIP(hipMalloc(&s.p, sizeof(double) * doubles));
-        s.doubles = doubles;
-    }
-    *p = s.p;
-    return 0;
-}
-
-inline unsigned project_blocks(long threads)
-{
-    const long b = (threads + 255) / 256;
-    return (unsigned)(b < 1 ? 1 : (b > kProjectBlocksMax ? kProjectBlocksMax : b));
+    return g_table.with(st, [&](ProjectScratch &s) -> int {
+        if (s.doubles < doubles) {
+            if (s.p) (void)hipFree(s.p);       // (hipFree waits for the device: no stage still reads the old buffer)
+            s.p = nullptr; s.doubles = 0;
+            PDEHIP_HIP(hipMalloc(&s.p, sizeof(double) * doubles));
+            s.doubles = doubles;
+        }
+        *p = s.p;
+        return 0;
+    });
 }
 
 // what a stage reads
@@ -220,29 +205,15 @@ struct Stage {
 template <class OP>
 void launch_stage(bool row, const Stage &s, unsigned blocks, int ncomp, hipStream_t st, const ProjectArgs &a)
 {
-#define PDEHIP_PROJECT(T, V)                                                                                                      \
-    do {                                                                                                                          \
-        if (row) hipLaunchKernelGGL((project_row_kernel<T, V, OP>), dim3(blocks, ncomp), dim3(256), 0, st, a);                    \
-        else hipLaunchKernelGGL((project_march_kernel<T, V, OP>), dim3(blocks, ncomp), dim3(256), 0, st, a);                      \
-    } while (0)
-    if (s.f64) {
-        if (s.vec == 2) PDEHIP_PROJECT(double, 2); else PDEHIP_PROJECT(double, 1);
-    } else {
-        if (s.vec == 4) PDEHIP_PROJECT(float, 4); else PDEHIP_PROJECT(float, 1);
-    }
-#undef PDEHIP_PROJECT
+    dispatch_piece(s.f64 ? PDEHIP_F64 : PDEHIP_F32, s.vec, [&](auto type, auto width) {
+        typedef decltype(type) T;
+        constexpr int V = decltype(width)::value;
+        if (row) hipLaunchKernelGGL((project_row_kernel<T, V, OP>), dim3(blocks, ncomp), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((project_march_kernel<T, V, OP>), dim3(blocks, ncomp), dim3(256), 0, st, a);
+    });
 }
 
 }  // namespace
-
-int project_release_scratch()
-{
-    std::lock_guard<std::mutex> lock(g_mu);
-    for (auto &e : g_table) (void)hipFree(e.second.p);
-    g_table.clear();
-    return 0;
-}
-
 }  // namespace pdehip
 
 using namespace pdehip;
@@ -268,7 +239,7 @@ extern "C" int pdehip_project(const pdehip_grid_t *g, int ncomp, const void *arr
 
     Stage s;
     s.g = make_row_grid(n); s.cs = n.pc; s.ptr = arr_full; s.f64 = f64;
-    s.vec = f64 ? (n.n[2] % 2 == 0 ? 2 : 1) : (n.n[2] % 4 == 0 ? 4 : 1);
+    s.vec = piece_width(n, arr_full, nullptr);      // (the field is on a 16-byte boundary: checked above)
     // the first stage leaves the largest intermediate array
     const long rows = n.n[0] * n.n[1];
     size_t half = 0;
@@ -323,7 +294,7 @@ extern "C" int pdehip_project(const pdehip_grid_t *g, int ncomp, const void *arr
         } else {
             a.out = scratch + (size_t)turn * half * ncomp;
         }
-        const unsigned blocks = project_blocks(threads);
+        const unsigned blocks = blocks_for(threads, kProjectBlocksMax);
         if (sum) launch_stage<OpSum>(row, s, blocks, ncomp, st, a);
         else launch_stage<OpMaxNan>(row, s, blocks, ncomp, st, a);
         len += snprintf(name + len, sizeof(name) - len, "%sproject_%s_kernel<%s,%d,%s>", len ? "+" : "", row ? "row" : "march",
@@ -357,7 +328,7 @@ extern "C" int pdehip_extract_box(const pdehip_grid_t *g, int ncomp, const void 
             PDEHIP_FAIL(E_VALUE, "extract_box: axis %d: [%ld, %ld + %ld) is not a box inside %ld cells", d, lo[d], lo[d], extent[d], n.n[ax]);
         a.lo[ax] = lo[d]; a.n[ax] = extent[d];
     }
-    const unsigned blocks = project_blocks(a.n[0] * a.n[1] * a.n[2]);
+    const unsigned blocks = blocks_for(a.n[0] * a.n[1] * a.n[2], kProjectBlocksMax);
     if (n.dtype == PDEHIP_F64) hipLaunchKernelGGL((extract_box_kernel<double>), dim3(blocks, ncomp), dim3(256), 0, as_stream(stream), a);
     else hipLaunchKernelGGL((extract_box_kernel<float>), dim3(blocks, ncomp), dim3(256), 0, as_stream(stream), a);
     note_kernel("extract_box_kernel<%s>", n.dtype == PDEHIP_F64 ? "double" : "float");

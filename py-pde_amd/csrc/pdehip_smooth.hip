@@ -26,10 +26,10 @@
 //   kMarchRadiusMax = (5120 / 32 - 64) / 2 = 48      ((64 + 2r) x 32 doubles)
 // Launches are capped at kSmoothBlocksMax workgroups per component; what is beyond takes a grid-stride turn.  No atomics, every output
 // has one writer and one order: two calls give equal bits.
-#include <map>
-#include <mutex>
-
 #include "pdehip_common.h"
+#include "pdehip_pieces.h"
+#include "pdehip_scratch.h"
+#include "pdehip_sweep.h"
 
 namespace pdehip {
 namespace {
@@ -73,18 +73,8 @@ __device__ __forceinline__ I resolve(I p, I n, int mode)
     return q < n ? q : m - 1 - q;
 }
 
-template <typename T, int VEC>
-__device__ __forceinline__ void load_cells(const T *p, T (&v)[VEC])
-{
-    if constexpr (VEC == 1) {
-        v[0] = p[0];
-    } else {
-        typedef T vec_t __attribute__((ext_vector_type(VEC)));
-        const vec_t x = *(const vec_t *)p;
-#pragma unroll
-        for (int q = 0; q < VEC; q++) v[q] = x[q];
-    }
-}
+// VEC fp64 results in one access, each rounded once to the field's type (beside store_piece of pdehip_pieces.h, not an overload of it:
+// for an fp64 field the two would be one signature)
 template <typename T, int VEC>
 __device__ __forceinline__ void store_cells(T *p, const double (&v)[VEC])
 {
@@ -159,7 +149,7 @@ __global__ void __launch_bounds__(256) gauss_march_kernel(SmoothArgs a, const T 
         if (inside)
             for (int s = ty; s < len + 2 * r; s += RY) {
                 T v[VEC];
-                load_cells<T, VEC>(in + base + (long)resolve<int>(y0 + s - r, n, a.mode) * a.ps, v);
+                load_piece<T, VEC>(in + base + (long)resolve<int>(y0 + s - r, n, a.mode) * a.ps, v);
 #pragma unroll
                 for (int k = 0; k < VEC; k++) tile[s * kMarchWidth + tx * VEC + k] = (double)v[k];
             }
@@ -218,8 +208,8 @@ struct WeightRing {
     bool pending[kWeightSlots] = {};
     unsigned turn = 0;
 };
-std::mutex g_mu;
-std::map<hipStream_t, WeightRing> g_table;
+int release_rings();
+StreamTable<WeightRing> g_table(release_rings);
 
 void free_ring(WeightRing &s)
 {
@@ -234,45 +224,33 @@ void free_ring(WeightRing &s)
     s.doubles = 0;
 }
 
+int release_rings() { return g_table.release(free_ring); }
+
 int stage_weights(hipStream_t st, const double *weights, size_t count, const double **dev)
 {
-    std::lock_guard<std::mutex> lock(g_mu);
-    WeightRing &s = g_table[st];
-    if (s.doubles < count) {
-        free_ring(s);
-        size_t cap = 64;
-        while (cap < count) cap *= 2;
-        PDEHIP_HIP(hipMalloc(&s.dev, sizeof(double) * cap * kWeightSlots));
-        PDEHIP_HIP(hipHostMalloc((void **)&s.pinned, sizeof(double) * cap * kWeightSlots, hipHostMallocDefault));
-        for (int k = 0; k < kWeightSlots; k++) PDEHIP_HIP(hipEventCreateWithFlags(&s.copied[k], hipEventDisableTiming));
-        s.doubles = cap;
-    }
-    const unsigned k = s.turn++ % kWeightSlots;
-    if (s.pending[k]) PDEHIP_HIP(hipEventSynchronize(s.copied[k]));
-    double *host = s.pinned + k * s.doubles, *device = s.dev + k * s.doubles;
-    memcpy(host, weights, sizeof(double) * count);
-    PDEHIP_HIP(hipMemcpyAsync(device, host, sizeof(double) * count, hipMemcpyHostToDevice, st));
-    PDEHIP_HIP(hipEventRecord(s.copied[k], st));
-    s.pending[k] = true;
-    *dev = device;
-    return 0;
-}
-
-inline unsigned smooth_blocks(long wanted)
-{
-    return (unsigned)(wanted < 1 ? 1 : (wanted > kSmoothBlocksMax ? kSmoothBlocksMax : wanted));
+    return g_table.with(st, [&](WeightRing &s) -> int {
+        if (s.doubles < count) {
+            free_ring(s);
+            size_t cap = 64;
+            while (cap < count) cap *= 2;
+            PDEHIP_HIP(hipMalloc(&s.dev, sizeof(double) * cap * kWeightSlots));
+            PDEHIP_HIP(hipHostMalloc((void **)&s.pinned, sizeof(double) * cap * kWeightSlots, hipHostMallocDefault));
+            for (int k = 0; k < kWeightSlots; k++) PDEHIP_HIP(hipEventCreateWithFlags(&s.copied[k], hipEventDisableTiming));
+            s.doubles = cap;
+        }
+        const unsigned k = s.turn++ % kWeightSlots;
+        if (s.pending[k]) PDEHIP_HIP(hipEventSynchronize(s.copied[k]));
+        double *host = s.pinned + k * s.doubles, *device = s.dev + k * s.doubles;
+        memcpy(host, weights, sizeof(double) * count);
+        PDEHIP_HIP(hipMemcpyAsync(device, host, sizeof(double) * count, hipMemcpyHostToDevice, st));
+        PDEHIP_HIP(hipEventRecord(s.copied[k], st));
+        s.pending[k] = true;
+        *dev = device;
+        return 0;
+    });
 }
 
 }  // namespace
-
-int smooth_release_scratch()
-{
-    std::lock_guard<std::mutex> lock(g_mu);
-    for (auto &e : g_table) free_ring(e.second);
-    g_table.clear();
-    return 0;
-}
-
 }  // namespace pdehip
 
 using namespace pdehip;
@@ -314,24 +292,21 @@ extern "C" int pdehip_smooth_axis(const pdehip_grid_t *g, int ncomp, const void 
     hipLaunchKernelGGL((kernel), dim3(blocks, ncomp), dim3(256), 0, st, a, (const T *)in_full, (T *)out_full, w)
     if (fits && a.axis == 2 && radius <= kRowRadiusMax) {
         const long pieces = n.n[0] * n.n[1] * ((n.n[2] + kRowLanes - 1) / kRowLanes);
-        const unsigned blocks = smooth_blocks((pieces + kRowPieces - 1) / kRowPieces);
+        const unsigned blocks = clamp_blocks((pieces + kRowPieces - 1) / kRowPieces, kSmoothBlocksMax);
         if (f64) PDEHIP_SMOOTH(gauss_row_kernel<double>, double, blocks);
         else PDEHIP_SMOOTH(gauss_row_kernel<float>, float, blocks);
         note_kernel("gauss_row_kernel<%s>", type);
     } else if (fits && a.axis < 2 && radius <= kMarchRadiusMax) {
         const long tiles = a.nq * ((a.na + kMarchLength - 1) / kMarchLength) * ((n.n[2] + kMarchWidth - 1) / kMarchWidth);
-        const unsigned blocks = smooth_blocks(tiles);
-        const int vec = f64 ? (n.n[2] % 2 == 0 ? 2 : 1) : (n.n[2] % 4 == 0 ? 4 : 1);
-        if (f64) {
-            if (vec == 2) PDEHIP_SMOOTH((gauss_march_kernel<double, 2>), double, blocks);
-            else PDEHIP_SMOOTH((gauss_march_kernel<double, 1>), double, blocks);
-        } else {
-            if (vec == 4) PDEHIP_SMOOTH((gauss_march_kernel<float, 4>), float, blocks);
-            else PDEHIP_SMOOTH((gauss_march_kernel<float, 1>), float, blocks);
-        }
+        const unsigned blocks = clamp_blocks(tiles, kSmoothBlocksMax);
+        const int vec = piece_width(n, in_full, out_full);      // (both arrays are on 16-byte boundaries: checked above)
+        dispatch_piece(n.dtype, vec, [&](auto t, auto width) {
+            typedef decltype(t) T;
+            PDEHIP_SMOOTH((gauss_march_kernel<T, decltype(width)::value>), T, blocks);
+        });
         note_kernel("gauss_march_kernel<%s,%d>", type, vec);
     } else {
-        const unsigned blocks = smooth_blocks((n.n[0] * n.n[1] * n.n[2] + 255) / 256);
+        const unsigned blocks = blocks_for(n.n[0] * n.n[1] * n.n[2], kSmoothBlocksMax);
         if (f64) PDEHIP_SMOOTH(gauss_cell_kernel<double>, double, blocks);
         else PDEHIP_SMOOTH(gauss_cell_kernel<float>, float, blocks);
         note_kernel("gauss_cell_kernel<%s>", type);

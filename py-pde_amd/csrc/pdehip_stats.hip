@@ -6,11 +6,9 @@
 // Every sweep: workgroups of 256 threads through blocks_for, the interior rows through for_row_pieces<VEC> (16-byte loads where the row
 // length allows), per wave a butterfly and one store per column into the wave's slot, then ONE workgroup that folds the slots in a
 // fixed order.  No atomics: two runs give equal bits.  Compiled without FMA contraction in every build.
-#include <map>
-#include <mutex>
-
 #include "pdehip_common.h"
 #include "pdehip_pieces.h"
+#include "pdehip_scratch.h"
 #include "pdehip_sweep.h"
 
 namespace pdehip {
@@ -162,49 +160,36 @@ __global__ void __launch_bounds__(256) steady_finish_kernel(SteadyArgs a, int ns
 // (calls on one stream are ordered; two streams reducing at the same time must not share one: sum_scratch, pdehip_ops.hip), allocated at
 // the stream's first call and kept until pdehip_release_scratch.
 struct StatsScratch { double *sums, *pairs; };      // three columns of sums, two columns of extrema
-std::mutex g_mu;
-std::map<hipStream_t, double *> g_table;
+int release_slots();
+StreamTable<double *> g_table(release_slots);
+
+int release_slots()
+{
+    return g_table.release([](double *p) { (void)hipFree(p); });   // (hipFree waits for the device: no sweep still reads the slots)
+}
 
 int stats_scratch(hipStream_t st, StatsScratch *s)
 {
-    std::lock_guard<std::mutex> lock(g_mu);
-    auto it = g_table.find(st);
-    if (it == g_table.end()) {
-        double *p = nullptr;
-        PDEHIP_HIP(hipMalloc(&p, sizeof(double) * 5 * kSweepWavesMax));
-        it = g_table.emplace(st, p).first;
-    }
-    s->sums = it->second;
-    s->pairs = it->second + 3L * kSweepWavesMax;
-    return 0;
+    return g_table.with(st, [&](double *&p) -> int {
+        if (!p) PDEHIP_HIP(hipMalloc(&p, sizeof(double) * 5 * kSweepWavesMax));
+        s->sums = p;
+        s->pairs = p + 3L * kSweepWavesMax;
+        return 0;
+    });
 }
 
 template <bool NORM>
 void launch_stats(const NGrid &n, int vec, unsigned blocks, hipStream_t st, const StatsArgs &a, bool second)
 {
-#define PDEHIP_STATS(T, V)                                                                                              \
-    do {                                                                                                                \
-        if (second) hipLaunchKernelGGL((stats_m2_kernel<T, V, NORM>), dim3(blocks), dim3(256), 0, st, a);               \
-        else hipLaunchKernelGGL((stats_sweep_kernel<T, V, NORM>), dim3(blocks), dim3(256), 0, st, a);                   \
-    } while (0)
-    if (n.dtype == PDEHIP_F64) {
-        if (vec == 2) PDEHIP_STATS(double, 2); else PDEHIP_STATS(double, 1);
-    } else {
-        if (vec == 4) PDEHIP_STATS(float, 4); else PDEHIP_STATS(float, 1);
-    }
-#undef PDEHIP_STATS
+    dispatch_piece(n.dtype, vec, [&](auto type, auto width) {
+        typedef decltype(type) T;
+        constexpr int V = decltype(width)::value;
+        if (second) hipLaunchKernelGGL((stats_m2_kernel<T, V, NORM>), dim3(blocks), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((stats_sweep_kernel<T, V, NORM>), dim3(blocks), dim3(256), 0, st, a);
+    });
 }
 
 }  // namespace
-
-int stats_release_scratch()
-{
-    std::lock_guard<std::mutex> lock(g_mu);
-    for (auto &e : g_table) (void)hipFree(e.second);   // (hipFree waits for the device: no sweep still reads the slots)
-    g_table.clear();
-    return 0;
-}
-
 }  // namespace pdehip
 
 using namespace pdehip;
@@ -261,13 +246,9 @@ extern "C" int pdehip_steady_state(const pdehip_grid_t *g, int ncomp, const void
     a.elapsed = n.dtype == PDEHIP_F64 ? elapsed : (double)(float)elapsed;
     a.rtol = n.dtype == PDEHIP_F64 ? rtol : (double)(float)rtol;
     a.sums = s.sums; a.maxs = s.pairs; a.out = out_dev;
-    if (n.dtype == PDEHIP_F64) {
-        if (vec == 2) hipLaunchKernelGGL((steady_sweep_kernel<double, 2>), dim3(blocks), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((steady_sweep_kernel<double, 1>), dim3(blocks), dim3(256), 0, st, a);
-    } else {
-        if (vec == 4) hipLaunchKernelGGL((steady_sweep_kernel<float, 4>), dim3(blocks), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((steady_sweep_kernel<float, 1>), dim3(blocks), dim3(256), 0, st, a);
-    }
+    dispatch_piece(n.dtype, vec, [&](auto type, auto width) {
+        hipLaunchKernelGGL((steady_sweep_kernel<decltype(type), decltype(width)::value>), dim3(blocks), dim3(256), 0, st, a);
+    });
     hipLaunchKernelGGL(steady_finish_kernel, dim3(1), dim3(256), 0, st, a, (int)blocks * 4);
     note_kernel("steady_sweep_kernel<%s,%d>", n.dtype == PDEHIP_F64 ? "double" : "float", vec);
     PDEHIP_HIP(hipGetLastError());

@@ -1,6 +1,7 @@
 // pdehip_sweep.h — what the pointwise sweeps of the device-side loops (pdehip_fixedpoint.hip, pdehip_poisson.hip, pdehip_poisson_mg.hip)
-// share in the offline build: the row loop, the launch geometry, the final sum of the wave partials (wave_partials, pdehip_device.h, is
-// the other half) and the read-back of a control block.
+// and of the analysis kernels (pdehip_stats.hip, pdehip_hist.hip, pdehip_project.hip; pdehip_smooth.hip takes the clamp) share in the
+// offline build: the row loop, alone and with loads in flight, the launch geometry, the final sum, minimum or maximum of the wave partials
+// (wave_partials, pdehip_device.h, is the other half) and the read-back of a control block.
 #pragma once
 
 #include "pdehip_common.h"
@@ -29,16 +30,39 @@ __device__ __forceinline__ void for_row_pieces(const RowGrid &g, F &&fn)
         fn(i, j, k, g.off + i * g.p0 + j * g.p1 + k);
     }
 }
+// The row loop of for_row_pieces<VEC> with the loads of kAhead pieces issued before the first of them is used: what is done per cell
+// there (pdehip_hist.hip: a search, votes, LDS adds) is long enough to leave the memory idle behind a single load per thread.
+// load(element, values) fills the values of a piece, use(values) consumes them; the order per thread is fixed.
+constexpr int kAhead = 4;
+template <typename T, int VEC, class L, class U>
+__device__ __forceinline__ void for_row_pieces_ahead(const RowGrid &g, L &&load, U &&use)
+{
+    const long per_row = g.n2 / VEC;
+    const long total = g.n0 * g.n1 * per_row;
+    const long stride = (long)gridDim.x * blockDim.x;
+    for (long t = blockIdx.x * (long)blockDim.x + threadIdx.x; t < total; t += kAhead * stride) {
+        T v[kAhead][VEC];
+#pragma unroll
+        for (int u = 0; u < kAhead; u++) {
+            const long tu = t + u * stride < total ? t + u * stride : t;      // (past the end: the first piece once more, not used)
+            long rest = tu;
+            const long k = (rest % per_row) * VEC; rest /= per_row;
+            const long j = rest % g.n1;
+            const long i = rest / g.n1;
+            load(g.off + i * g.p0 + j * g.p1 + k, v[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < kAhead; u++)
+            if (t + u * stride < total) use(v[u]);
+    }
+}
 __device__ __forceinline__ int wave_slot() { return (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)); }
 
 // workgroups of 256 threads for `items` pieces; the cap bounds the waves of a launch and with them the slots a loop needs
 constexpr long kSweepBlocksMax = 8192;
 constexpr int kSweepWavesMax = (int)(kSweepBlocksMax * (256 / 64));
-inline unsigned blocks_for(long items)
-{
-    const long b = (items + 255) / 256;
-    return (unsigned)(b < 1 ? 1 : (b > kSweepBlocksMax ? kSweepBlocksMax : b));
-}
+inline unsigned clamp_blocks(long wanted, long cap) { return (unsigned)(wanted < 1 ? 1 : (wanted > cap ? cap : wanted)); }
+inline unsigned blocks_for(long items, long cap = kSweepBlocksMax) { return clamp_blocks((items + 255) / 256, cap); }
 // launch of a row sweep over `cells` cells: `kernel` names its instance with VEC, which is 2 where the row length is even, else 1
 #define PDEHIP_LAUNCH_ROWS(even, cells, st, kernel, ...)                                                                              \
     do {                                                                                                                             \

@@ -23,7 +23,7 @@ import operator
 import numpy as np
 
 from .device import DeviceArray, DeviceBuffer
-from .statistics import resident_link
+from .resident import backend_of, device_source, is_collection
 
 BINS_MAX = 4096
 QUANTILES_PER_CALL = 8
@@ -190,27 +190,15 @@ def _check_q(q) -> np.ndarray:
     return q
 
 
-def device_usable(backend, dev: DeviceArray) -> bool:
-    """Real components (no planar complex pairs), at most 64 of them, and a library that has the entry points."""
-    return not dev.complex_pairs and dev.ncomp <= 64 and backend._lib.has("histogram", "quantile_select", "field_stats")
-
-
-def _is_collection(obj) -> bool:
-    return getattr(obj, "fields", None) is not None or getattr(obj, "_fields", None) is not None
-
-
 class DistributionMixin:
     """``make_histogram`` and ``make_quantiles`` of :class:`~pde_hip.backend.HipBackendMixin`."""
 
     def _distribution_source(self, obj, grid):
         """(device array or None, getter of the host data ``(*components, *grid)`` and the number of its component axes)."""
-        dev = obj if isinstance(obj, DeviceArray) else None
-        if dev is None and not _is_collection(obj):
-            link = resident_link(obj)
-            if link is not None:
-                dev = link.dev_state
-        if dev is not None and device_usable(self, dev):
-            return dev, None
+        if not is_collection(obj):      # (a collection: the host path, whatever its state)
+            dev, _ = device_source(self, obj, needs=("histogram", "quantile_select", "field_stats"))
+            if dev is not None:
+                return dev, None
 
         def host():
             if isinstance(obj, DeviceArray):
@@ -346,21 +334,15 @@ class DistributionMixin:
 
 
 # ---- module level ----------------------------------------------------------------------------------------------------------------------
-def _backend_of(field, backend):
-    from .projection import _backend_of as resolve
-
-    return resolve(field, backend)
-
-
 def field_histogram(state, bins=10, range=None, *, density: bool = False, norm: bool = False, backend="hip") -> FieldHistogram:
     """Histogram of ``state`` (a py-pde or a mirror field, or a :class:`DeviceArray`) - on the device while its state is resident there,
     else on the host: ``pde_hip.field_histogram(state, 64, (-1, 1)).counts`` inside a tracker costs a few hundred bytes instead of the state."""
-    return _backend_of(state, backend).make_histogram()(state, bins, range, density=density, norm=norm)
+    return backend_of(state, backend).make_histogram()(state, bins, range, density=density, norm=norm)
 
 
 def field_quantile(state, q, *, method: str = "linear", norm: bool = False, ignore_nan: bool = False, backend="hip"):
     """Quantiles of ``state`` over the grid, per component (see :meth:`DistributionMixin.make_quantiles`)."""
-    return _backend_of(state, backend).make_quantiles()(state, q, method=method, norm=norm, ignore_nan=ignore_nan)
+    return backend_of(state, backend).make_quantiles()(state, q, method=method, norm=norm, ignore_nan=ignore_nan)
 
 
 def field_median(state, *, method: str = "linear", norm: bool = False, ignore_nan: bool = False, backend="hip"):

@@ -23,7 +23,7 @@ import itertools
 import numpy as np
 
 from .device import DeviceArray, DeviceBuffer
-from .statistics import resident_link
+from .resident import backend_of, is_collection, resident_link
 
 
 class FieldDomains:
@@ -136,10 +136,6 @@ def host_domains(mask: np.ndarray, periodic, connectivity: int = 1):
     return labels.astype(np.int32), int(count)
 
 
-def _is_collection(obj) -> bool:
-    return getattr(obj, "fields", None) is not None or getattr(obj, "_fields", None) is not None
-
-
 def _refuse_components(what: str, comp_shape) -> None:
     first = ", ".join("0" for _ in comp_shape)
     msg = (f"field_domains: {what} has components {tuple(comp_shape)}; domains are those of ONE component - pass a scalar, for instance "
@@ -182,11 +178,13 @@ class DomainsMixin:
         per axis, default the grid's (all open for a bare array without a grid).  ``grid``: the grid of bare arrays; a field brings its own."""
 
         def label(obj, threshold=0.0, *, above: bool = True, interval=None, connectivity: int = 1, periodic=None) -> FieldDomains:
-            if _is_collection(obj):
+            if is_collection(obj):
                 _refuse_components("a collection", (len(list(obj)),))
             field_grid = getattr(obj, "grid", None) if not isinstance(obj, DeviceArray) else None
             if field_grid is None:
                 field_grid = grid
+            # (not `device_source`: the refusals below, and the shape and type of the host path, read the device array whether or not
+            # the kernels take it)
             dev = obj if isinstance(obj, DeviceArray) else None
             link = None if dev is not None else resident_link(obj)
             if link is not None:
@@ -235,7 +233,5 @@ class DomainsMixin:
 def field_domains(state, threshold=0.0, *, above: bool = True, interval=None, connectivity: int = 1, periodic=None, backend="hip") -> FieldDomains:
     """The domains of ``state`` (a py-pde or a mirror scalar field, or a :class:`DeviceArray`) - on the device while its state is resident
     there, else on the host: ``pde_hip.field_domains(state).sizes`` inside a tracker costs one number per droplet instead of the state."""
-    from .projection import _backend_of
-
-    return _backend_of(state, backend).make_domain_labeller()(state, threshold, above=above, interval=interval, connectivity=connectivity,
+    return backend_of(state, backend).make_domain_labeller()(state, threshold, above=above, interval=interval, connectivity=connectivity,
                                                               periodic=periodic)

@@ -16,6 +16,7 @@ import numpy as np
 from . import _abi
 from .device import DeviceArray, DeviceBuffer
 from .faces import real_dtype_of
+from .resident import base_class, field_dtype, valid_link
 
 
 class DomainError(ValueError):
@@ -89,18 +90,6 @@ def _planar(host: np.ndarray, lead: int) -> np.ndarray:
     return np.stack([host.real, host.imag], axis=lead)
 
 
-def _resident_link(field):
-    """The :class:`~pde_hip.resident.ResidentState` of a field whose device copy is current, else None."""
-    link = getattr(field, "__dict__", {}).get("_hip_link")
-    return link if link is not None and not link.host_touched else None
-
-
-def _field_dtype(field) -> np.dtype:
-    """dtype of the field's data without touching the host arrays of a resident state (``field.dtype`` reads ``_data_full``: a pull)."""
-    link = _resident_link(field)
-    return np.dtype(link.dev_state.host_dtype if link is not None else field.dtype)
-
-
 class InterpolationMixin:
     """``make_interpolator`` of :class:`~pde_hip.backend.HipBackendMixin`."""
 
@@ -140,7 +129,7 @@ class InterpolationMixin:
         _require_cartesian(grid)
         num_axes = len(grid.shape)
         data_shape = (grid.dim,) * int(field.rank)
-        dtype = _field_dtype(field)
+        dtype = field_dtype(field)
         _abi.dtype_code(real_dtype_of(dtype))            # float64 / float32 (and their complex pairs) only
         fill_host = _convert_fill(fill, data_shape, dtype)
         source = _Source(grid)
@@ -148,7 +137,7 @@ class InterpolationMixin:
         state: dict = {}
 
         def own_data():
-            link = _resident_link(field)
+            link = valid_link(field)
             if link is not None and not with_ghost_cells:
                 return link.dev_state              # the device copy is current: nothing crosses PCIe but points and values
             # with_ghost_cells: the ghost cells are the HOST array's (the caller set them there), so a resident state is pulled first
@@ -214,7 +203,7 @@ class InterpolationMixin:
         device copy of a resident state is used in place: only its ghost cells are written."""
         grid = field.grid
         bcs = grid.get_boundary_conditions(bc, rank=int(field.rank))
-        link = _resident_link(field)
+        link = valid_link(field)
         if link is not None:
             # Only ghost cells of the live state are written.  Nothing reads them as they are left here: every operator and every
             # stepper sweep sets the ghost cells of its operand from its own conditions before the stencil reads them, and a pull
@@ -236,7 +225,7 @@ class InterpolationMixin:
             raise error_classes()[1](msg)
         _require_cartesian(grid, "interpolate_to_grid")
         data_shape = (src.dim,) * int(field.rank)
-        dtype = _field_dtype(field)
+        dtype = field_dtype(field)
         fill_host = _convert_fill(fill, data_shape, dtype)
         lib = self._lib
         if not lib.has("interpolate_to_grid"):
@@ -245,7 +234,7 @@ class InterpolationMixin:
         if bc is not None:
             dev, cplx = self._full_with_corners(field, bc), False
         else:
-            link = _resident_link(field)
+            link = valid_link(field)
             data = link.dev_state if link is not None else field.data
             dev, cplx, _ = self._to_interp_source(src, data, data_shape, False)
         out = DeviceArray(self.grid_info(grid, dev.dtype), dev.comp_shape, complex_pairs=cplx)
@@ -266,8 +255,7 @@ class InterpolationMixin:
         if outside.value:
             raise error_classes()[0](_OOB_MESSAGE)
         values = out.get_valid(stream=self.stream)
-        cls = getattr(type(field), "_hip_base_class", type(field))
-        return cls(grid, values.astype(dtype, copy=False), label=label)
+        return base_class(field)(grid, values.astype(dtype, copy=False), label=label)
 
 
 def interpolate_to_grid(field, grid, *, bc=None, fill=None, label=None, backend="hip"):

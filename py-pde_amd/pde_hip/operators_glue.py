@@ -20,6 +20,7 @@ from ._lib import require_device
 from .device import DeviceArray, DeviceBuffer, DeviceScalar, GridInfo, ptr_array
 from .evaluation import _ExpressionEvaluation
 from .faces import convert_bcs, make_face_setter, real_dtype_of
+from .resident import resident_link
 
 _logger = logging.getLogger("pde_hip.backend")
 
@@ -115,13 +116,14 @@ class OperatorGlueMixin:
         (:class:`ResidentState`), 8 bytes per component cross PCIe instead of the whole state.  Host data is checked on the host."""
 
         def is_finite(obj) -> bool:
+            # (not `device_source`: this reduction takes every device array - complex pairs, any number of components - and a library
+            # without its entry point is an error, not a host path)
             arr = obj
             if not isinstance(obj, DeviceArray):
-                link = getattr(obj, "__dict__", {}).get("_hip_link")
-                if link is not None and link.host_stale:       # the device copy is the current one
-                    arr = link.dev_state
-                else:
+                link = resident_link(obj)
+                if link is None:               # the host copy is the current one
                     return bool(np.all(np.isfinite(getattr(obj, "data", obj))))
+                arr = link.dev_state
             out = DeviceBuffer(8 * arr.ncomp)
             self._lib.count_nonfinite(arr.info.ref, arr.ncomp, arr.ptr, out.ptr, self.stream)
             host = np.empty(arr.ncomp, dtype=np.float64)

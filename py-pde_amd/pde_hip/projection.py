@@ -23,7 +23,7 @@ import numpy as np
 
 from . import _abi
 from .device import DeviceArray, DeviceBuffer
-from .statistics import resident_link
+from .resident import DeviceOption, backend_of, base_class, device_source, is_collection
 
 _METHOD_CODES = {"integral": _abi.PROJECT_SUM, "average": _abi.PROJECT_SUM, "mean": _abi.PROJECT_SUM, "maximum": _abi.PROJECT_MAX,
                  "max": _abi.PROJECT_MAX, "minimum": _abi.PROJECT_MIN, "min": _abi.PROJECT_MIN}
@@ -213,26 +213,14 @@ def finish_image(field, data: dict, transpose: bool) -> dict:
 
 
 # ---- which objects the device answers for ------------------------------------------------------------------------------------------
-def _base_class(obj) -> type:
-    return getattr(type(obj), "_hip_base_class", type(obj))
-
-
-def _is_collection(obj) -> bool:
-    return getattr(obj, "fields", None) is not None or getattr(obj, "_fields", None) is not None
-
-
 def device_copy(backend, obj):
     """The :class:`DeviceArray` a projection of ``obj`` reads on the device, or None (the host path): a bare array of real components,
     or the resident state of a real scalar field while the device copy is the current one."""
-    if not backend._lib.has("project", "extract_box"):
-        return None
-    if isinstance(obj, DeviceArray):
-        return obj if not obj.complex_pairs and obj.ncomp <= 64 else None
-    link = resident_link(obj)
-    if link is None or _is_collection(obj) or int(getattr(obj, "rank", 0)) != 0:
-        return None
-    dev = link.dev_state
-    return dev if not dev.complex_pairs and dev.comp_shape == () else None
+    dev, bare = device_source(backend, obj, needs=("project", "extract_box"))
+    if dev is None or bare:
+        return dev
+    scalar = not is_collection(obj) and int(getattr(obj, "rank", 0)) == 0 and dev.comp_shape == ()
+    return dev if scalar else None
 
 
 def _grid_of(obj, grid):
@@ -245,25 +233,11 @@ def _grid_of(obj, grid):
 class ProjectionMixin:
     """``make_projector`` and ``make_slicer`` of :class:`~pde_hip.backend.HipBackendMixin`."""
 
-    @property
-    def device_projections(self) -> bool:
+    device_projections = DeviceOption(
         """Whether ``project`` / ``slice`` / ``get_line_data`` / ``get_image_data`` of a real scalar field whose state is resident on the
         device are answered there, without a download (``config["backend.hip.device_projections"]`` with py-pde,
         ``backend.device_projections = True`` stand-alone).  Default False: a device sum differs from numpy's in the last bits, and
-        bit-for-bit behaviour is the default."""
-        value = getattr(self, "_device_projections", None)
-        if value is not None:
-            return value
-        try:
-            if "device_projections" in self.config:
-                return bool(self.config["device_projections"])
-        except TypeError:
-            pass
-        return False
-
-    @device_projections.setter
-    def device_projections(self, value) -> None:
-        self._device_projections = None if value is None else bool(value)
+        bit-for-bit behaviour is the default.""")
 
     # --- the two calls ----------------------------------------------------------------------------------------------------------
     def _result_buffer(self, nbytes: int) -> DeviceBuffer:
@@ -321,14 +295,14 @@ class ProjectionMixin:
         tensor fields (the reference has no ``project`` for them: the bare array of the projected components)."""
 
         def project(obj, axes, *, method: str = "integral", label=None):
-            if _is_collection(obj):
+            if is_collection(obj):
                 return [project(f, axes, method=method, label=label) for f in obj]
             field_grid = _grid_of(obj, grid)
             ax_remove, ax_retain = parse_axes(field_grid, axes)
             dev = device_copy(self, obj) if len(set(ax_remove)) == len(ax_remove) and method in _METHOD_CODES else None
             if dev is None and not isinstance(obj, DeviceArray):
-                if int(getattr(obj, "rank", 0)) == 0 and hasattr(_base_class(obj), "project"):
-                    return _base_class(obj).project(obj, axes, method=method, label=label)
+                if int(getattr(obj, "rank", 0)) == 0 and hasattr(base_class(obj), "project"):
+                    return base_class(obj).project(obj, axes, method=method, label=label)
                 return host_project(field_grid, np.asarray(obj.data), ax_remove, method)       # (reads `data`: a resident state comes down)
             bare = isinstance(obj, DeviceArray)
             sliced = None if bare else field_grid.slice(ax_retain)
@@ -340,7 +314,7 @@ class ProjectionMixin:
                 data = self._device_mean(dev, ax_remove, removed_weight(field_grid, ax_remove))
             else:
                 data = self.device_project(dev, ax_remove, _METHOD_CODES[method])
-            return data if bare else _base_class(obj)(grid=sliced, data=data, label=label)
+            return data if bare else base_class(obj)(grid=sliced, data=data, label=label)
 
         return project
 
@@ -351,15 +325,15 @@ class ProjectionMixin:
         are removed.  Device and host path as for :meth:`make_projector`; the bits are numpy's on either."""
 
         def slice_(obj, position, *, label=None):
-            if _is_collection(obj):
+            if is_collection(obj):
                 return [slice_(f, position, label=label) for f in obj]
             field_grid = _grid_of(obj, grid)
             values, ax_retain = parse_position(field_grid, position)
             dev = device_copy(self, obj)
             bare = isinstance(obj, DeviceArray)
             if dev is None and not bare:
-                if int(getattr(obj, "rank", 0)) == 0 and hasattr(_base_class(obj), "slice"):
-                    return _base_class(obj).slice(obj, position, label=label)
+                if int(getattr(obj, "rank", 0)) == 0 and hasattr(base_class(obj), "slice"):
+                    return base_class(obj).slice(obj, position, label=label)
                 cells = nearest_cells(field_grid, values)
                 data = np.asarray(obj.data)
                 lead = data.ndim - field_grid.num_axes
@@ -371,7 +345,7 @@ class ProjectionMixin:
                 lead = data.ndim - field_grid.num_axes
                 return data[(slice(None),) * lead + tuple(cells.get(ax, slice(None)) for ax in range(field_grid.num_axes))]
             data = self._device_cut(dev, cells)
-            return data if bare else _base_class(obj)(grid=sliced, data=data, label=label)
+            return data if bare else base_class(obj)(grid=sliced, data=data, label=label)
 
         return slice_
 
@@ -384,11 +358,11 @@ class ProjectionMixin:
             raise TypeError(msg)
         dev = device_copy(self, obj)
         if dev is None:
-            return _base_class(obj).get_line_data(obj, extract=extract)
+            return base_class(obj).get_line_data(obj, extract=extract)
         grid = obj.grid
         kind, axis = parse_extract(grid, extract)
         if not 0 <= axis < grid.num_axes:
-            return _base_class(obj).get_line_data(obj, extract=extract)
+            return base_class(obj).get_line_data(obj, extract=extract)
         others = [ax for ax in range(grid.num_axes) if ax != axis]
         if kind == "cut" or not others:
             data_y = self._device_cut(dev, {ax: grid.shape[ax] // 2 for ax in others} if kind == "cut" else {})
@@ -403,7 +377,7 @@ class ProjectionMixin:
             raise TypeError(msg)
         dev = device_copy(self, obj)
         if dev is None or obj.grid.num_axes not in (2, 3):
-            return _base_class(obj).get_image_data(obj, transpose=transpose)
+            return base_class(obj).get_image_data(obj, transpose=transpose)
         grid = obj.grid
         image = self._device_cut(dev, {2: grid.shape[2] // 2} if grid.num_axes == 3 else {})
         return finish_image(obj, _image_dict(grid, image), transpose)
@@ -424,43 +398,25 @@ class _ArrayGrid:
 
 
 # ---- module level: pde_hip.project(field, axes) ... ---------------------------------------------------------------------------------
-def _backend_of(field, backend):
-    link = getattr(field, "__dict__", {}).get("_hip_link")
-    if link is not None:
-        return link.backend
-    if not isinstance(backend, str):
-        return backend
-    probe = next(iter(field), field) if _is_collection(field) else field
-    if type(probe).__module__.split(".")[0] == "pde":
-        from pde.backends import get_backend as pde_get_backend
-
-        from . import pypde_plugin  # noqa: F401  (registers "hip")
-
-        return pde_get_backend(backend)
-    from .backend import get_backend
-
-    return get_backend(backend)
-
-
 def project(field, axes, *, method: str = "integral", label=None, backend="hip"):
     """``field.project(axes, method=method, label=label)`` - on the device while the state of a real scalar field is resident there, else
     on the host: ``pde_hip.project(state, "z", method="mean")`` inside a tracker costs a plane instead of the state."""
-    return _backend_of(field, backend).make_projector()(field, axes, method=method, label=label)
+    return backend_of(field, backend).make_projector()(field, axes, method=method, label=label)
 
 
 def slice_field(field, position, *, label=None, backend="hip"):
     """``field.slice(position, label=label)``, on the device while the state is resident there."""
-    return _backend_of(field, backend).make_slicer()(field, position, label=label)
+    return backend_of(field, backend).make_slicer()(field, position, label=label)
 
 
 def line_data(field, extract: str = "auto", *, backend="hip") -> dict:
     """``field.get_line_data(extract=extract)``, on the device while the state is resident there."""
-    return _backend_of(field, backend).line_data(field, extract)
+    return backend_of(field, backend).line_data(field, extract)
 
 
 def image_data(field, *, transpose: bool = False, backend="hip") -> dict:
     """``field.get_image_data(transpose=transpose)``, on the device while the state is resident there."""
-    return _backend_of(field, backend).image_data(field, transpose)
+    return backend_of(field, backend).image_data(field, transpose)
 
 
 # ---- the methods of a resident field, answered from the device (opt-in: `device_projections`) ------------------------------------------
@@ -470,7 +426,7 @@ def device_method(link, field, name: str):
     backend = link.backend
     if device_copy(backend, field) is None:
         return None
-    reference = getattr(_base_class(field), name)
+    reference = getattr(base_class(field), name)
     if name == "project":
         def method(axes, *, method="integral", label=None):
             return backend.make_projector()(field, axes, method=method, label=label)

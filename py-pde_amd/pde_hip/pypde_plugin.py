@@ -40,6 +40,7 @@ import numpy as np
 from . import operators as _operators
 from .backend import HipBackendMixin
 from .device import DeviceArray
+from .resident import link_of, resident_link
 
 DEFAULT_CONFIG = {
     "device": Parameter(value=-1, cls=int, description="Index of the HIP device (MI355X) the backend runs on; `hip:<n>` overrides it. "
@@ -403,7 +404,7 @@ class HipConsistencyTracker(_trackers.ConsistencyTracker):
     name = "hip_consistency"
 
     def handle(self, field, t: float) -> None:
-        link = getattr(field, "__dict__", {}).get("_hip_link")
+        link = link_of(field)
         if link is None:
             return super().handle(field, t)
         if not link.backend.make_finite_check()(field):
@@ -430,9 +431,9 @@ class HipSteadyStateTracker(_trackers.SteadyStateTracker):
     def handle(self, field, t: float) -> None:
         from .statistics import device_usable
 
-        link = getattr(field, "__dict__", {}).get("_hip_link")
+        link = resident_link(field)
         check = self._check
-        on_device = (link is not None and link.host_stale and not self.progress and self.evolution_rate is None
+        on_device = (link is not None and not self.progress and self.evolution_rate is None
                      and device_usable(link.backend, link.dev_state))
         if not on_device:
             if check.started:                     # the snapshot goes back to where the parent keeps it
@@ -463,8 +464,8 @@ class HipMaterialConservationTracker(_trackers.MaterialConservationTracker):
         """The magnitudes from the device, or None where the host path applies."""
         from .statistics import NOT_ANSWERED, device_property
 
-        link = getattr(field, "__dict__", {}).get("_hip_link")
-        if link is None or not link.host_stale:
+        link = resident_link(field)
+        if link is None:
             return None
         name = "magnitudes" if isinstance(field, pde.FieldCollection) else "magnitude"
         value = device_property(link, field, name)

@@ -29,7 +29,7 @@ import numpy as np
 
 from . import _abi
 from .device import DeviceArray
-from .statistics import resident_link
+from .resident import DeviceOption, ResidentState, backend_of, base_class, field_dtype, is_collection, link_of, resident_link
 
 
 # ---- scipy's weights and scipy's arithmetic, in numpy ---------------------------------------------------------------------------------
@@ -109,11 +109,11 @@ def mirror_smooth_collection(collection, sigma: float = 1, *, out=None, label=No
 
 def assert_field_compatible(field, other) -> None:
     """``FieldBase.assert_field_compatible`` (pde/fields/base.py:371-395); a py-pde field checks itself."""
-    own = getattr(_base_class(field), "assert_field_compatible", None)
+    own = getattr(base_class(field), "assert_field_compatible", None)
     if own is not None:
         own(field, other)
         return
-    if _base_class(field) is not _base_class(other):
+    if base_class(field) is not base_class(other):
         msg = f"Fields {field} and {other} are incompatible"
         raise TypeError(msg)
     if field.grid != other.grid:
@@ -122,14 +122,6 @@ def assert_field_compatible(field, other) -> None:
 
 
 # ---- which objects the device answers for ------------------------------------------------------------------------------------------
-def _base_class(obj) -> type:
-    return getattr(type(obj), "_hip_base_class", type(obj))
-
-
-def _is_collection(obj) -> bool:
-    return getattr(obj, "fields", None) is not None or getattr(obj, "_fields", None) is not None
-
-
 def _is_cartesian(grid) -> bool:
     if not all(hasattr(grid, a) for a in ("shape", "discretization", "periodic")):
         return False
@@ -143,41 +135,21 @@ def _valid_sigma(sigma) -> bool:
         return False
 
 
-def _field_dtype(field) -> np.dtype:
-    """The type of the field's data without touching ``field.data`` (py-pde's ``dtype`` reads it: a resident state would come down)."""
-    link = getattr(field, "__dict__", {}).get("_hip_link")
-    return np.dtype(link.dev_state.host_dtype if link is not None else field.dtype)
-
-
 def _device_field(field) -> bool:
     """A real fp64 / fp32 field of at most 64 components on a Cartesian grid."""
-    if _is_collection(field) or not _is_cartesian(getattr(field, "grid", None)):
+    if is_collection(field) or not _is_cartesian(getattr(field, "grid", None)):
         return False
-    dtype = _field_dtype(field)
+    dtype = field_dtype(field)
     return dtype in (np.float64, np.float32) and field.grid.num_axes ** int(getattr(field, "rank", 0)) <= 64
 
 
 class SmoothingMixin:
     """``make_smoother`` of :class:`~pde_hip.backend.HipBackendMixin`."""
 
-    @property
-    def device_smoothing(self) -> bool:
+    device_smoothing = DeviceOption(
         """Whether ``state.smooth(...)`` of a real field whose state is resident on the device is answered there, without a download
         (``config["backend.hip.device_smoothing"]`` with py-pde, ``backend.device_smoothing = True`` stand-alone).  Default False: with
-        the default, nothing that existed before this option changes its path.  ``pde_hip.smooth`` does not depend on it."""
-        value = getattr(self, "_device_smoothing", None)
-        if value is not None:
-            return value
-        try:
-            if "device_smoothing" in self.config:
-                return bool(self.config["device_smoothing"])
-        except TypeError:
-            pass
-        return False
-
-    @device_smoothing.setter
-    def device_smoothing(self, value) -> None:
-        self._device_smoothing = None if value is None else bool(value)
+        the default, nothing that existed before this option changes its path.  ``pde_hip.smooth`` does not depend on it.""")
 
     # --- the passes -------------------------------------------------------------------------------------------------------------
     def _smooth_work(self, info, comp_shape, slot: int) -> DeviceArray:
@@ -257,19 +229,20 @@ class SmoothingMixin:
                 return _host_path(obj, sigma, out, label)
             if out is not None and out is not obj:
                 assert_field_compatible(obj, out)
-                if _field_dtype(out) != _field_dtype(obj):
+                if field_dtype(out) != field_dtype(obj):
                     return _host_path(obj, sigma, out, label)
             field_grid = obj.grid
             link = resident_link(obj)
             if link is not None and (link.dev_state.complex_pairs or link.dev_state.comp_shape != (obj.grid.num_axes,) * int(getattr(obj, "rank", 0))):
                 return _host_path(obj, sigma, out, label)
             comp_shape = (field_grid.num_axes,) * int(getattr(obj, "rank", 0))
-            staged = self._smooth_work(self.grid_info(field_grid, _field_dtype(obj)), comp_shape, 2)
+            staged = self._smooth_work(self.grid_info(field_grid, field_dtype(obj)), comp_shape, 2)
             if link is not None:
                 src = link.dev_state
             else:
                 src = staged
-                _plain_data(obj, lambda: src.set_valid(obj.data, self.stream))
+                with ResidentState.plain_access(obj):
+                    src.set_valid(obj.data, self.stream)
             if out is obj and link is not None:
                 # in place on the device: `dev_state` keeps its address (steppers hold it), the host copy stays stale, nothing moves
                 self.device_smooth(src, src, sigma, field_grid.periodic)
@@ -281,11 +254,12 @@ class SmoothingMixin:
             # a host result: the passes end in work array 2 (an uploaded source lies there already: in place), then one download
             res = self.device_smooth(src, staged, sigma, field_grid.periodic)
             if out is None:
-                out = _base_class(obj)(field_grid, "empty", label=obj.label, dtype=_field_dtype(obj))
-            target = getattr(out, "__dict__", {}).get("_hip_link")
+                out = base_class(obj)(field_grid, "empty", label=obj.label, dtype=field_dtype(obj))
+            target = link_of(out)
             if target is not None:      # a resident field as the destination: its host copy becomes the current one
                 target.pull(out)
-            _plain_data(out, lambda: res.get_valid(out=out.data, stream=self.stream), write=True)
+            with ResidentState.plain_access(out, write=True):
+                res.get_valid(out=out.data, stream=self.stream)
             if label:
                 out.label = label
             return out
@@ -293,25 +267,9 @@ class SmoothingMixin:
         return smooth
 
 
-def _plain_data(field, action, write: bool = False):
-    """``action()`` reads or writes ``field.data`` as plain host memory: the interception of a resident field is off meanwhile; after
-    a write the next stepper call uploads the host copy."""
-    link = getattr(field, "__dict__", {}).get("_hip_link")
-    if link is None:
-        return action()
-    field.__dict__["_hip_link"] = None
-    try:
-        result = action()
-    finally:
-        field.__dict__["_hip_link"] = link
-    if write:
-        link.host_touched = True
-    return result
-
-
 def _host_path(obj, sigma, out, label):
     """The reference's arithmetic: the field's own method (py-pde's runs scipy, the mirror classes' the numpy restatement)."""
-    return _base_class(obj).smooth(obj, sigma, out=out, label=label)
+    return base_class(obj).smooth(obj, sigma, out=out, label=label)
 
 
 # ---- module level: pde_hip.smooth(field, sigma) -----------------------------------------------------------------------------------------
@@ -319,9 +277,7 @@ def smooth(field, sigma=1, *, out=None, label=None, device: bool = False, backen
     """``field.smooth(sigma, out=out, label=label)`` - on the device: the resident copy of a state is read where it is, host data is
     uploaded once.  ``device=True`` returns the result as a :class:`~pde_hip.device.DeviceArray` (for ``pde_hip.field_statistics``, the
     projector and the slicer of the backend) and ``out=field`` smooths a resident state in place, both without a download."""
-    from .projection import _backend_of
-
-    return _backend_of(field, backend).make_smoother()(field, sigma, out=out, label=label, device=device)
+    return backend_of(field, backend).make_smoother()(field, sigma, out=out, label=label, device=device)
 
 
 # ---- the method of a resident field, answered from the device (opt-in: `device_smoothing`) ---------------------------------------------
@@ -330,7 +286,7 @@ def device_method(link, field, name: str):
     backend = link.backend
     if name != "smooth" or not _device_field(field) or not backend._lib.has("smooth_axis") or link.dev_state.complex_pairs:
         return None
-    reference = getattr(_base_class(field), name)
+    reference = getattr(base_class(field), name)
 
     def method(sigma=1, *, out=None, label=None):
         return backend.make_smoother()(field, sigma, out=out, label=label)

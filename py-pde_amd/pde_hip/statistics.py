@@ -19,16 +19,11 @@ from __future__ import annotations
 import numpy as np
 
 from .device import DeviceArray, DeviceBuffer
+from .resident import DeviceOption, backend_of, device_source, kernels_take, link_of
 
 _EMPTY_MAX = "zero-size array to reduction operation maximum which has no identity"      # numpy's message for np.max of nothing
 STAT_PROPERTIES = frozenset({"integral", "average", "fluctuations", "magnitude"})
 COLLECTION_PROPERTIES = frozenset({"integrals", "averages", "magnitudes"})
-
-
-def resident_link(obj):
-    """The :class:`ResidentState` of a field whose DEVICE copy is the current one (``host_stale``), else None."""
-    link = getattr(obj, "__dict__", {}).get("_hip_link")
-    return link if link is not None and link.host_stale else None
 
 
 def _geometry(grid, info=None) -> tuple[float, float]:
@@ -125,32 +120,21 @@ def _host_raw(values: np.ndarray, lead: int, variance: bool) -> np.ndarray:
     return raw.reshape(comp_shape + (8,))
 
 
+_NEEDS = ("field_stats", "steady_state")
+
+
 def device_usable(backend, dev: DeviceArray) -> bool:
     """Real components (no planar complex pairs) and a library that has the two entry points."""
-    return not dev.complex_pairs and backend._lib.has("field_stats", "steady_state")
+    return kernels_take(backend, dev, _NEEDS, max_comp=None)
 
 
 class StatisticsMixin:
     """``make_statistics`` and ``make_steady_state_check`` of :class:`~pde_hip.backend.HipBackendMixin`."""
 
-    @property
-    def device_statistics(self) -> bool:
+    device_statistics = DeviceOption(
         """Whether ``integral`` / ``average`` / ``fluctuations`` / ``magnitude`` of a field whose state is resident on the device are
         answered there, without a download (``config["backend.hip.device_statistics"]`` with py-pde, ``backend.device_statistics = True``
-        stand-alone).  Default False: a device sum differs from numpy's in the last bits, and bit-for-bit behaviour is the default."""
-        value = getattr(self, "_device_statistics", None)
-        if value is not None:
-            return value
-        try:
-            if "device_statistics" in self.config:
-                return bool(self.config["device_statistics"])
-        except TypeError:
-            pass
-        return False
-
-    @device_statistics.setter
-    def device_statistics(self, value) -> None:
-        self._device_statistics = None if value is None else bool(value)
+        stand-alone).  Default False: a device sum differs from numpy's in the last bits, and bit-for-bit behaviour is the default.""")
 
     def _device_raw(self, dev: DeviceArray, norm: bool, variance: bool) -> np.ndarray:
         blocks = 1 if norm else dev.ncomp
@@ -178,13 +162,9 @@ class StatisticsMixin:
             field_grid = getattr(obj, "grid", None)
             if field_grid is None:
                 field_grid = grid
-            dev = obj if isinstance(obj, DeviceArray) else None
-            if dev is None:
-                link = resident_link(obj)
-                if link is not None:
-                    dev = link.dev_state
-            if dev is not None and not device_usable(self, dev):
-                obj, dev = (obj if not isinstance(obj, DeviceArray) else dev.get_valid(stream=self.stream)), None
+            dev, bare = device_source(self, obj, needs=_NEEDS, max_comp=None)      # (more than 64 components: refused by name below)
+            if dev is None and bare:
+                obj = obj.get_valid(stream=self.stream)
             if dev is not None:
                 cell, volume = _geometry(field_grid, dev.info)
                 comp_shape = () if norm else dev.comp_shape
@@ -192,7 +172,7 @@ class StatisticsMixin:
                 host_derived = None
                 if raw[:, 1].any():
                     # non-finite cells: numpy's derived quantities differ from the finite-cell statistics; take them from the pulled state
-                    data = dev.get_valid(stream=self.stream) if isinstance(obj, DeviceArray) else np.asarray(obj.data)
+                    data = dev.get_valid(stream=self.stream) if bare else np.asarray(obj.data)
                     host_derived = _derived_on_host(data, len(dev.comp_shape), len(dev.info.shape), cell, volume, norm, variance)
                 return FieldStatistics(raw, comp_shape, cell, volume, on_device=True, host_derived=host_derived)
             data = np.asarray(getattr(obj, "data", obj))
@@ -276,15 +256,12 @@ class SteadyStateCheck:
         return bool(value <= self.atol)
 
     def _device_state(self, obj):
-        backend = self.backend
-        dev = obj if isinstance(obj, DeviceArray) else None
-        if dev is None:
-            link = resident_link(obj)
-            if link is not None:
-                dev, backend = link.dev_state, self.backend or link.backend
-        if dev is None or backend is None or not device_usable(backend, dev):
+        backend = self.backend or getattr(link_of(obj), "backend", None)      # (a tracker's check learns its backend from the state)
+        if backend is None:
             return None
-        self.backend = backend
+        dev, _ = device_source(backend, obj, needs=_NEEDS, max_comp=None)
+        if dev is not None:
+            self.backend = backend
         return dev
 
     def update(self, obj, t: float):
@@ -331,22 +308,7 @@ class SteadyStateCheck:
 def field_statistics(field, *, variance: bool = False, norm: bool = False, backend="hip") -> FieldStatistics:
     """Statistics of ``field`` (a py-pde or a mirror field, or a :class:`DeviceArray`) - on the device while its state is resident
     there, else on the host: ``pde_hip.field_statistics(state, variance=True).fluctuations``."""
-    link = getattr(field, "__dict__", {}).get("_hip_link")
-    if link is not None:
-        impl = link.backend
-    elif not isinstance(backend, str):
-        impl = backend
-    elif type(field).__module__.split(".")[0] == "pde":
-        from pde.backends import get_backend as pde_get_backend
-
-        from . import pypde_plugin  # noqa: F401  (registers "hip")
-
-        impl = pde_get_backend(backend)
-    else:
-        from .backend import get_backend
-
-        impl = get_backend(backend)
-    return impl.make_statistics()(field, variance=variance, norm=norm)
+    return backend_of(field, backend).make_statistics()(field, variance=variance, norm=norm)
 
 
 # ---- the properties of a resident field, answered from the device (opt-in: `device_statistics`) -------------------------------------
