@@ -1044,6 +1044,40 @@ int pdehip_label_domains(const pdehip_grid_t *g, const void *arr_full, double lo
                          const int *periodic_host, int32_t *labels_dev, uint64_t *info_dev, void *stream);
 int pdehip_domain_sizes(const int32_t *labels_dev, int64_t ncells, int64_t ndomains, uint64_t *sizes_dev, void *stream);
 
+/* pdehip_domain_properties (optional entry point; the ABI version stays 8): where every domain of a labelling is, what box it fills and
+ * how much of the field it holds - what `scipy.ndimage.center_of_mass`, `find_objects` and `sum_labels` answer on the host.  All outputs
+ * are integers: they do not depend on the order in which workgroups run and two calls give equal bits; centroids, boxes and sums are
+ * derived from them on the host (pde_hip/domains.py).  labels_dev: dense C-ordered int32 labels of the interior shape of g (0:
+ * background, 1 ... ndomains), those of pdehip_label_domains or any other.  Axes are normalised to three (an n-D grid has the trailing n;
+ * a missing axis has one cell, is open, and its columns are 0); n_a is the interior extent of axis a, periodic_host as above.  Domain k
+ * (label k + 1) receives
+ *     anchor_dev[k]                int32: the smallest C-order linear interior index among its cells
+ *     moment_dev[3 k + a]          int64: the sum over its cells of the frame offset d_a = i_a - i_a(anchor) on an open axis,
+ *                                  ((i_a - i_a(anchor) + h) mod n_a) - h with h = n_a / 2 (integer division, mathematical mod) on a
+ *                                  periodic one - the minimal image relative to the anchor
+ *     box_dev[6 k + 2 a], [+ 1]    int32: the smallest and the largest d_a
+ * and, with arr_full != NULL (ONE real component in the device layout, fp64 or fp32 as g says),
+ *     excluded_dev[k]              uint32: its cells whose value is not finite or exceeds absmax in magnitude; they add nothing below
+ *     limb_dev[2 k], [+ 1]         int64: the sums of hi and lo over its other cells, where with L = ceil(log2(interior cells)), E the
+ *                                  exponent frexp(absmax) returns, eh = E - (62 - L), el = eh - 31 and v the value converted exactly
+ *                                  to fp64: hi = rint(ldexp(v, -eh)), r = v - ldexp(hi, eh) (exact), lo = rint(ldexp(r, -el)).
+ *                                  The sum of the field over the domain is ldexp(limb[0], eh) + ldexp(limb[1], el), within 2^(el - 1) per
+ *                                  cell; |hi| <= 2^(62 - L) and |lo| <= 2^30, so neither 64-bit sum overflows.  absmax == 0: zero limbs.
+ *                                  absmax is below 2^1023, so that ldexp(hi, eh) <= 2^E is finite.
+ * With arr_full == NULL limb_dev and excluded_dev are not touched.  A label without a cell keeps anchor INT32_MAX, box (INT32_MAX,
+ * INT32_MIN) and zeros.  ndomains == 0 writes nothing (the outputs may be NULL).  72 bytes per domain in all.
+ * Three launches: initialisation; `props_anchor_kernel` (atomicMin per (wave, label)); `props_sum_kernel<T,FIELD>`, in which the lanes of
+ * a wave that share a label are combined by a masked wave reduction and a wave keeps the label it met last with its partial results in
+ * registers, as in pdehip_domain_sizes: one set of relaxed agent-scope integer atomics (64-bit adds, 32-bit min / max) per (wave, label).
+ * No floating-point atomic anywhere.  Labels outside 0 ... ndomains are counted, never used as an index: if there is one the call is
+ * refused with their number (PDEHIP_E_VALUE).  The call waits for the stream to read that count (the caller reads the results next);
+ * 16 bytes each of device and pinned host memory are kept per stream and freed by pdehip_release_scratch.  pdehip_last_kernel_name
+ * names the instance of the last kernel.  Also refused: NULL or misaligned pointers (16 bytes for the field, 8 for moments and limbs, 4
+ * for the others), ndomains outside 0 ... 2^31 - 1, more than 2^31 - 1 interior cells, unsupported types, an absmax that is negative, NaN or not below 2^1023. */
+int pdehip_domain_properties(const pdehip_grid_t *g, const void *arr_full, const int32_t *labels_dev, int64_t ndomains,
+                             const int *periodic_host, double absmax, int32_t *anchor_dev, int64_t *moment_dev, int32_t *box_dev,
+                             int64_t *limb_dev, uint32_t *excluded_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,7 +18,7 @@ from . import operators as _operators
 from .backend import HipBackend, get_backend
 from .boundaries import BoundariesList
 from .distribution import FieldHistogram, field_histogram, field_median, field_quantile
-from .domains import FieldDomains, field_domains
+from .domains import FieldDomains, domain_properties, field_domains
 from .fields import FieldCollection, ScalarField, Tensor2Field, VectorField
 from .grids import CartesianGrid, UnitGrid
 from .interpolation import interpolate_to_grid
@@ -61,6 +61,7 @@ __all__ = [
     "UnitGrid",
     "VectorField",
     "field_domains",
+    "domain_properties",
     "field_histogram",
     "field_median",
     "field_quantile",

@@ -379,6 +379,8 @@ OPTIONAL_PROTOTYPES: dict[str, list] = {
     # connected domains of the cells inside an interval, numbered like scipy.ndimage.label, and their sizes (csrc/pdehip_label.hip)
     "label_domains": [_pg, _vp, _d, _d, _i, C.POINTER(_i), _vp, _vp, _vp],
     "domain_sizes": [_vp, _i64, _i64, _vp, _vp],
+    # anchors, offset sums, boxes and fixed-point field sums of labelled domains (csrc/pdehip_props.hip)
+    "domain_properties": [_pg, _vp, _vp, _i64, C.POINTER(_i), _d, _vp, _vp, _vp, _vp, _vp, _vp],
 }
 
 PROJECT_SUM, PROJECT_MAX, PROJECT_MIN = 0, 1, 2
