@@ -156,7 +156,8 @@ const char *pdehip_last_kernel_name(void);
  * expression order, results bit-identical to its numpy / torch-CPU evaluation.  1: the same kernels compiled with FMA contraction - what
  * numba's default `fastmath` (pde/backends/numba/utils.py:330-336; config `backend.numba.fastmath`, pde/backends/numba/config.py:20-26) allows
  * the reference's own numba backend; results agree with the exact build within 1e-10 relative (tests/test_hip_fastmath.py), ~10-20 % fewer
- * fp64 operations per cell.  Set it before building steppers: kernels of expression PDEs are compiled for the mode current at their first use. */
+ * fp64 operations per cell.  Per call, every kernel instance is held to the rounding-error bound of its own expression - an FMA only removes a
+ * rounding, nothing is reassociated - against a reference in extended precision (tests/test_hip_fastmath_instances.py, tests/fastmath_cases.py).  Set it before building steppers: kernels of expression PDEs are compiled for the mode current at their first use. */
 int pdehip_set_fastmath(int on);
 int pdehip_get_fastmath(int *on);
 int pdehip_abi_version(void);

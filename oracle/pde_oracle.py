@@ -10,6 +10,7 @@ All arrays are host numpy arrays in the "full" (ghost padded) layout unless note
 
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import subprocess
 import sys
@@ -35,20 +36,26 @@ def build(force: bool = False) -> Path:
     return so
 
 
+def _load(so: Path):
+    """Open one build of the oracle and bind its prototypes."""
+    handle = C.CDLL(str(so))
+    for name, (args, _) in _abi.COMPUTE_PROTOTYPES.items():
+        if name in {"hostfull_to_full", "full_to_hostfull"}:
+            continue  # the oracle's full layout IS the reference's compact host layout
+        fn = getattr(handle, "oracle_" + name)
+        fn.argtypes = args
+        fn.restype = C.c_int
+    handle.oracle_set_corner_points_2d.argtypes = [C.POINTER(_abi.Grid), C.POINTER(C.c_int), C.c_void_p]
+    handle.oracle_set_corner_points_2d.restype = C.c_int
+    return handle
+
+
 def lib():
     """Load (building first if necessary) the oracle library and bind its prototypes."""
     global _LIB
     if _LIB is None:
         so = build()
-        handle = C.CDLL(str(so))
-        for name, (args, _) in _abi.COMPUTE_PROTOTYPES.items():
-            if name in {"hostfull_to_full", "full_to_hostfull"}:
-                continue  # the oracle's full layout IS the reference's compact host layout
-            fn = getattr(handle, "oracle_" + name)
-            fn.argtypes = args
-            fn.restype = C.c_int
-        handle.oracle_set_corner_points_2d.argtypes = [C.POINTER(_abi.Grid), C.POINTER(C.c_int), C.c_void_p]
-        handle.oracle_set_corner_points_2d.restype = C.c_int
+        handle = _load(so)
         # OpenMP threads: what this process may really use (affinity mask and cgroup CPU quota) — the GPU boxes show 256
         # logical CPUs but grant 16: 256 threads on 16 CPUs run the loops tens of times slower
         import os
@@ -70,6 +77,28 @@ def lib():
                 pass
         _LIB = handle
     return _LIB
+
+
+_FAST_LIB = None
+
+
+@contextlib.contextmanager
+def fastmath_build():
+    """Inside the block every function of this module runs ``libpde_oracle_fastmath.so``: the same restatement compiled with FMA contraction,
+    reassociation and reciprocal maths (``oracle/Makefile``: FASTFLAGS).  Never a parity checker - tests/test_fastmath_cases_cpu.py uses it as a
+    real contracted build that a rounding-error bound has to hold for."""
+    global _LIB, _FAST_LIB
+    exact = lib()
+    if _FAST_LIB is None:
+        so = _HERE / "libpde_oracle_fastmath.so"
+        if not so.exists():
+            subprocess.run(["make", "-C", str(_HERE), "-s", so.name], check=True)
+        _FAST_LIB = _load(so)
+    _LIB = _FAST_LIB
+    try:
+        yield
+    finally:
+        _LIB = exact
 
 
 def _p(arr: np.ndarray | None):

@@ -325,6 +325,7 @@ static int launch_div_t(const NGrid &n, DivArgs a, hipStream_t st)
     PDEHIP_DIV(4) PDEHIP_DIV(2) PDEHIP_DIV(1)
 #undef PDEHIP_DIV
     PDEHIP_HIP(hipGetLastError());
+    note_kernel("div_march_kernel<%s,%d,RY=2,CZ=%d,method=%d,%s>", sizeof(T) == 8 ? "double" : "float", VEC, cz, METHOD, n.ndim == 3 ? "3-D" : "2-D");
     return 0;
 }
 
