@@ -980,6 +980,7 @@ int pdehip_jit_euler_run(const pdehip_grid_t *g, const pdehip_jit_pass_t *passes
                 if (it != j->cache.end()) v = it->second;
                 else PDEHIP_TRY(compile_variant(j, key, false, tname, n.dtype == PDEHIP_F64 ? 2 : 4, mode, tcw, false, true, &v, kTileVariant));
                 void *kargs[] = {&ta};
+                note_kernel("tile2d_kernel<%s,mode=%d,32x%d tile> (%d steps per launch, time levels in LDS; run-time built)", tname, mode, tcw, k);
                 PDEHIP_HIP(hipModuleLaunchKernel(v.fn, nblocks, 1, 1, 1024, 1, 1, 0, as_stream(stream), kargs, nullptr));
                 s += k;
                 char *t = cur; cur = nxt; nxt = t;

@@ -777,6 +777,12 @@ def _cases():
                         out.append(Case(family="launch_tile2d", entry="euler_multi_2d", shape=shape, dtype=dtype, bounds=((0.0, 1.0 * shape[0]), (0.0, 0.9 * shape[1])),
                                         periodic=tuple(FACES[faces][0]), bc=("faces2d", faces), kind=kind,
                                         param=0.7 if kind == "diffusion" else 0.9, dt=0.05 if kind == "diffusion" else 1e-3, steps=steps, seed=3))
+    # the 64-column tile (tests/tile2d_cases.py: 2 x 128 tiles is the smallest grid that gets it): second row tile of one row, last tile column of two cells
+    for kind in ("diffusion", "cahn_hilliard"):
+        for dtype in (F64, F32):
+            out.append(Case(family="launch_tile2d", entry="euler_multi_2d", shape=(33, 8130), dtype=dtype, bounds=((0.0, 33.0), (0.0, 0.9 * 8130)),
+                            periodic=tuple(FACES["pl"][0]), bc=("faces2d", "pl"), kind=kind, param=0.7 if kind == "diffusion" else 0.9,
+                            dt=0.05 if kind == "diffusion" else 1e-3, steps=TILE2D_MAX_STEPS[kind], seed=3, opts=(("instance", "32x64 tile"),)))
     return out
 
 

@@ -122,7 +122,8 @@ def test_every_family_both_types_and_every_size_limit():
         types = {c.dtype for c in CASES if c.family == fam}
         assert types == ({"float64"} if fam == "launch_euler4" else {"float64", "float32"}), fam   # (the four-step sweep is fp64 only)
     for c in CASES:
-        assert c.cells <= 200_000 or c.shape == (33, 64, 128), c.id
+        # (the smallest grid of the unit-spacing four-step instance, and the smallest that gets the 64-column tile of the 2-D kernel: 268 290 cells)
+        assert c.cells <= 200_000 or c.shape in ((33, 64, 128), (33, 8130)), c.id
         assert 1 <= c.steps <= 8
     assert len(set(IDS)) == len(IDS)
 
