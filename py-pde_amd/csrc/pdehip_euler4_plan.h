@@ -65,6 +65,20 @@ constexpr int lane_patch(int t)
 static_assert(TY == 32 && TZ == 64 && PY == 2 && HALO == 4 && WAVES == 12, "lane_patch is written for this tile");
 static_assert(OWNER_WAVES * 64 == (TY / PY) * (TZ / 2), "the output patches fill the owner waves exactly");
 
+// The highest level lane t's patch is needed at - 4 for an output patch, 3 for a patch of ring 1, 1 for a patch of ring 0 (a patch k patches
+// from the rim holds the cells 2k and 2k + 1 from the rim, and a cell c from the rim is valid up to level c) - and 0 for the second copy of a
+// repeated patch, the one in the spare lanes 40 ... 63 of waves 9 and 10: the other copy does its work.  Inside waves 8 ... 10 the kernel
+// runs level l + 1 of a phase in the lanes with l < lane_levels(t) only (tests/test_euler4_lane_levels.py enumerates what that leaves).
+constexpr int lane_levels(int t)
+{
+    const int w = t >> 6, lane = t & 63;
+    if ((w == 9 || w == 10) && lane >= 40) return 0;
+    const int p = lane_patch(t), py = p / NPZ, pz = p - py * NPZ;
+    const int dy = py < NPY - 1 - py ? py : NPY - 1 - py, dz = pz < NPZ - 1 - pz ? pz : NPZ - 1 - pz;
+    const int ring = dy < dz ? dy : dz;
+    return 2 * ring + 1 < LEVELS ? 2 * ring + 1 : LEVELS;
+}
+
 // index (in doubles) of cell `cell` (0, 1) of row `row` (0 ... PY - 1) of patch `patch` at level `level` (0 ... LEVELS - 1)
 constexpr int image_index(int level, int row, int cell, int patch) { return GUARD + ((level * PY + row) * 2 + cell) * ARR + patch; }
 
@@ -127,7 +141,12 @@ constexpr int SCHEDULE_EVENTS = sizeof(SCHEDULE) / sizeof(SCHEDULE[0]);
 // one form of an expression that the kernel and the host probe can share from a header without HIP qualifiers.)
 #define PDEHIP_E4_MINUS_TWICE(x, c) __builtin_fma(-2.0, (c), (x))
 
-constexpr long MIN_CHUNK = 8;       // the fewest output planes of an x-chunk (each chunk recomputes 2 * HALO planes more)
+// The kernel addresses a cell as a plane's base (a wave-uniform pointer) plus the lane's byte offset inside the plane, an unsigned 32-bit
+// register: 8 * (off + row * p1 + column) with row * p1 + column < p0 (`off`: the first valid cell of the array, `p0`: the plane pitch, both
+// in doubles).  True when every such offset is below 2^32; the launcher declines otherwise.
+constexpr bool offsets_fit(long off, long p0) { return off >= 0 && p0 > 0 && off <= (1L << 29) && p0 <= (1L << 29) - off; }
+
+constexpr long MIN_CHUNK = 8;      // the fewest output planes of an x-chunk (each chunk recomputes 2 * HALO planes more)
 constexpr long WANT_CHUNK = 16;     // chunks are not made shorter than this to fill the chip
 constexpr long CUS = 256;           // one workgroup per CU (LDS)
 static_assert(RY % PY == 0 && HALO % PY == 0 && TZ % 2 == 0 && THREADS <= 1024 && LDS_BYTES <= 160 * 1024, "tile of the four-step sweep");

@@ -26,6 +26,8 @@ int launch_euler4(const NGrid &n, const void *in, void *out, double s1, double s
     const int knob = e4plan::knob_from_env();
     if (knob == 0 || e2plan::knobs().off || force_generic_kernels() || n.ndim != 3 || n.dtype != PDEHIP_F64 || in == out) return 0;
     if ((uintptr_t)in % 16 || (uintptr_t)out % 16 || n.off % 2 || n.p[0] % 2 || n.p[1] % 2 || n.p[0] >= (1L << 31)) return 0;
+    // a lane's byte offset inside a plane is a 32-bit register, and so is the number of a plane
+    if (!e4plan::offsets_fit(n.off, n.p[0]) || n.n[0] >= (1L << 30)) return 0;
     e4plan::Query q;
     q.elem = 8; q.ndim = n.ndim; q.n0 = n.n[0]; q.n1 = n.n[1]; q.n2 = n.n[2];
     for (int k = 0; k < 3; k++) q.per[k] = classify_axis(fg, k, n.n[k]);

@@ -11,7 +11,8 @@
 // consecutive planes in registers.  Neighbours inside the patch come from those registers; the others from the LDS image of the level's middle
 // plane.  The levels run skewed: iteration i (local planes count from the first loaded one) computes
 //     level 1 at plane i + 1,   level 2 at plane i,   level 3 at plane i - 1,   level 4 at plane i - 2   (stored from i = 6 on)
-// The loop is unrolled three times so that the rotation of the plane buffers is a renaming (like euler2_body).  What the first iterations
+// The loop is unrolled six times so that the rotation of the plane buffers (over three phases, like euler2_body) and the change of the
+// image buffers (over two, below) are both a renaming.  What the first iterations
 // compute from planes that do not exist yet (zeros) never reaches a stored cell: level L at plane p reads level L - 1 at p - 1 ... p + 1 only.
 //
 // The image (e4plan::image_index): per level, patch row and patch cell one array indexed by the patch number, sixteen arrays of 720 doubles
@@ -43,9 +44,19 @@
 //     (and its A);
 //   * image 0 is read before A and written behind it; its next read lies behind B;
 //   * image 3 is read before B and written behind it; its next read lies behind A of the next phase.
-// The stores of levels 1 and 2 are issued where their data is produced and nothing waits for them but the next barrier.  The buffer bases
-// are wave-uniform (scalar registers, swapped after B); a lane adds its patch number to them.  The prologue stores the middle planes of
-// iteration 0 (parity 0) into the buffers 0 and zeroes the second buffers with their guard runs, behind one barrier.
+// The stores of levels 1 and 2 are issued where their data is produced and nothing waits for them but the next barrier.  The parity is a
+// compile-time constant of the unrolled loop, so every access of either buffer is a lane's index register plus an immediate.  The prologue
+// stores the middle planes of iteration 0 (parity 0) into the buffers 0 and zeroes the second buffers with their guard runs, behind one barrier.
+//
+// A phase executes fp64 arithmetic, LDS and memory instructions and next to nothing else per lane (profiles/euler4_phase_diet_time.md: about
+// 17 integer and move instructions per wave and phase became about one):
+//   * a plane's base - input and output - is a wave-uniform pointer formed once per phase in scalar registers, and a row of a lane's patch
+//     is a loop-invariant 32-bit byte offset inside the plane (e4plan::offsets_fit; the launcher declines an array whose planes are larger):
+//     the loads and the non-temporal stores take the scalar base, and no lane adds 64-bit addresses;
+//   * the plane that is loaded goes straight into the slot of the plane that dies - what level 0 still needs of that one, old - 2 * mid, is
+//     taken first - so three register sets rotate through the unrolled phases and nothing is moved;
+//   * the loop has one exit: whole rounds of six phases, then the (at most five) phases left over.  Several exits shared a block that
+//     moved the live planes into common registers once per round.
 //
 // Waves have roles (e4plan::lane_patch, wave_levels; the lane -> patch map is not the row-major numbering of the image).  A patch is needed at
 // as many levels as its distance from the rim of the region allows - an output patch at all four, the ring around the outputs at levels
@@ -55,7 +66,10 @@
 // a SIMD.  Only the owner waves store to the field.  Every wave executes every barrier of every phase - the skips enclose no barrier - and
 // the trip count depends on the workgroup alone.  The cells of a skipped level keep the zeros of the prologue in the image; they are read
 // only by cells that are invalid at their own level, like the unspecified values above (tests/test_euler4_lanes.py enumerates it by lane
-// and by role: whatever a valid cell reads was stored by a wave that executes that level).  The results are the same bits as before.
+// and by role: whatever a valid cell reads was stored by a wave that executes that level).  The same holds lane by lane: inside the halo
+// waves 8 ... 10 a level runs only in the lanes whose patch is needed at it (e4plan::lane_levels, `lanes` below), the cells of a masked lane
+// keep the prologue's zeros too, and tests/test_euler4_lane_levels.py enumerates that a valid cell reads none of them.  The results are the
+// same bits as before.
 //
 // Per cell the arithmetic is `laplace` + `update` of pdehip_march2.inc (cartesian.py:220-227) in the same order: bit-identical to four single
 // steps in the exact build.  One thing is written differently: each `neighbour - 2 * centre` is one fused multiply-add (PDEHIP_E4_MINUS_TWICE:
@@ -89,18 +103,29 @@ __global__ void __launch_bounds__(e4plan::THREADS) euler4_kernel(const LapArgs a
     const int lx = (int)((a.n0 - x0 < (long)a.lx) ? a.n0 - x0 : (long)a.lx);
     auto wrap = [](long i, long n) { return i < 0 ? i + n : (i >= n ? i - n : i); };   // (n >= the tile / 16 planes: one wrap is enough)
 
-    long roff[PY];   // element offset of the patch's rows in a plane
+    // Addresses: a plane's base is a wave-uniform pointer (a scalar register pair, formed once per phase), a row of the patch a loop-invariant
+    // 32-bit byte offset of the lane inside the plane (e4plan::offsets_fit, asked by the launcher): loads and stores take the scalar base
+    // with a 32-bit lane offset, and no lane adds 64-bit addresses in the loop.
+    unsigned roff[PY];   // byte offset of the patch's rows in a plane
     const long zc = wrap(tz * TZ - HALO + lz, a.n2);           // even: a patch never straddles the wrap
 #pragma unroll
-    for (int r = 0; r < PY; r++) roff[r] = a.off + wrap(ty * TY - HALO + ly + r, a.n1) * a.p1 + zc;
-    const T *in = (const T *)a.in;
-    T *out = (T *)a.out;
-    auto plane_src = [&](int q) { return wrap(x0 - HALO + q, a.n0) * a.p0; };   // local plane q of level 0
+    for (int r = 0; r < PY; r++) roff[r] = (unsigned)((a.off + wrap(ty * TY - HALO + ly + r, a.n1) * a.p1 + zc) * (long)sizeof(T));
+    unsigned soff[PY];   // the same offsets once more, for the field stores (a copy that the stores' own block can pin)
+#pragma unroll
+    for (int r = 0; r < PY; r++) soff[r] = roff[r];
+    const char *in = (const char *)a.in;
+    char *out = (char *)a.out;
+    // local plane q of level 0, in bytes (the plane number in 32 bits, which the launcher asks for: a scalar compare, where 64 bits take a vector one)
+    const int x0i = (int)x0, n0i = (int)a.n0;
+    auto plane_src = [&](int q) {
+        const int x = x0i - HALO + q;
+        return (long)(x < 0 ? x + n0i : (x >= n0i ? x - n0i : x)) * a.p0 * (long)sizeof(T);
+    };
     const int qlast = lx + 2 * HALO - 1;
     auto load_plane = [&](int q, V (&dst)[PY]) {
-        const long po = plane_src(q < qlast ? q : qlast);      // (the prefetch behind the last plane repeats it)
+        const char *const base = in + plane_src(q < qlast ? q : qlast);      // (the prefetch behind the last plane repeats it)
 #pragma unroll
-        for (int r = 0; r < PY; r++) dst[r] = PDEHIP_LDV((const V *)(in + po + roff[r]));
+        for (int r = 0; r < PY; r++) dst[r] = PDEHIP_LDV((const V *)(base + roff[r]));
     };
 
     // The patch number twice.  Every array is read twice per level, at offsets a constant apart; through the same index the compiler merges
@@ -109,70 +134,61 @@ __global__ void __launch_bounds__(e4plan::THREADS) euler4_kernel(const LapArgs a
     int me2 = tid;
     asm volatile("" : "+v"(me2));
     if ((int)threadIdx.x < GUARD) lds[threadIdx.x] = lds[IMAGE - GUARD + threadIdx.x] = 0;   // (no result depends on it)
-    // The two buffers of image l = 1, 2 as bases that alt_index / alt_read_index are added to: cur[l - 1] is read in this phase, oth[l - 1]
-    // written; they change places after every phase (wave-uniform values: scalar moves, and one add per index register and phase).
-    // Buffer 0 is the level's part of `lds`, buffer 1 lies in the dynamic array.
+    // The two buffers of image l = 1, 2: buffer 0 is the level's part of `lds` (image_index, read_index), buffer 1 lies in the dynamic array
+    // (alt_index, alt_read_index).  Which of the two a phase reads is its parity, a compile-time constant of the unrolled loop: every access
+    // is an index register plus an immediate.
     LT *const alt = (LT *)euler4_alt;
-    LT *cur[ALT_LEVELS] = {(LT *)lds + (image_index(1, 0, 0, 0) - alt_index(1, 0, 0, 0)), (LT *)lds + (image_index(2, 0, 0, 0) - alt_index(2, 0, 0, 0))};
-    LT *oth[ALT_LEVELS] = {alt, alt};
     for (int k = (int)threadIdx.x; k < ALT_IMAGE; k += THREADS) alt[k] = 0;   // arrays and guard runs: a skipped level's cells stay zero
 
-    auto update = [&](double xm, double xp, double up, double dn, double left, double right, double cen) {
-        // (xm - 2 * cen) + xp and so on, as the reference rounds them
-        const double dx = PDEHIP_E4_MINUS_TWICE(xm, cen) + xp, dy = PDEHIP_E4_MINUS_TWICE(up, cen) + dn, dz = PDEHIP_E4_MINUS_TWICE(left, cen) + right;
+    auto update = [&](double dxm, double xp, double up, double dn, double left, double right, double cen) {
+        // (xm - 2 * cen) + xp and so on, as the reference rounds them; dxm = xm - 2 * cen comes from the caller
+        const double dx = dxm + xp, dy = PDEHIP_E4_MINUS_TWICE(up, cen) + dn, dz = PDEHIP_E4_MINUS_TWICE(left, cen) + right;
         if (M2 == E2_DIFFUSION_UNIT) return cen + a.s2 * (dx + dy + dz);   // all scales are exactly 1.0
         const double ex = dx * a.sx;
         const double ey = dy * a.sy;
         const double ez = dz * a.sz;
         return epilogue<LAP_EULER>(ex + ey + ez, cen, cen, a.s1, a.s2, a.gamma);
     };
-    // the eight neighbour cells of the patch in the image of level l
-    auto fetch = [&](int l, T (&nb)[READ_KINDS]) {
+    // old - 2 * mid: all that a level needs of its oldest plane
+    auto minus_twice = [&](const V (&old)[PY], const V (&mid)[PY], V (&d)[PY]) {
+#pragma unroll
+        for (int r = 0; r < PY; r++) d[r] = V{PDEHIP_E4_MINUS_TWICE(old[r][0], mid[r][0]), PDEHIP_E4_MINUS_TWICE(old[r][1], mid[r][1])};
+    };
+    // the eight neighbour cells of the patch in the image of level l, buffer `buf` (1: images 1 and 2 only)
+    auto fetch = [&](int l, int buf, T (&nb)[READ_KINDS]) {
 #pragma unroll
         for (int k = 0; k < READ_KINDS; k++) {
             const bool second = k == RD_BELOW1 || k == RD_LEFT1 || k == RD_RIGHT0 || k == RD_RIGHT1;   // the second read of its array
-            nb[k] = lds[read_index(l, k, second ? me2 : me)];
+            nb[k] = buf ? alt[alt_read_index(l, k, second ? me2 : me)] : lds[read_index(l, k, second ? me2 : me)];
         }
     };
-    // one level up: the plane of `mid` at the next level, from the thread's cells of three planes and the neighbours of the middle one
-    auto level = [&](const V (&old)[PY], const V (&mid)[PY], const V (&nw)[PY], const T (&nb)[READ_KINDS], V (&res)[PY]) {
+    // one level up: the plane of `mid` at the next level, from the thread's cells of three planes (the oldest as d = old - 2 * mid) and the
+    // neighbours of the middle one
+    auto level = [&](const V (&d)[PY], const V (&mid)[PY], const V (&nw)[PY], const T (&nb)[READ_KINDS], V (&res)[PY]) {
         const V above = V{nb[RD_ABOVE0], nb[RD_ABOVE1]}, below = V{nb[RD_BELOW0], nb[RD_BELOW1]};
 #pragma unroll
         for (int r = 0; r < PY; r++) {
             const double left = nb[RD_LEFT0 + r], right = nb[RD_RIGHT0 + r];
             const V up = r == 0 ? above : mid[r > 0 ? r - 1 : 0], dn = r == PY - 1 ? below : mid[r < PY - 1 ? r + 1 : r];
-            res[r][0] = update(old[r][0], nw[r][0], up[0], dn[0], left, mid[r][1], mid[r][0]);
-            res[r][1] = update(old[r][1], nw[r][1], up[1], dn[1], mid[r][0], right, mid[r][1]);
+            res[r][0] = update(d[r][0], nw[r][0], up[0], dn[0], left, mid[r][1], mid[r][0]);
+            res[r][1] = update(d[r][1], nw[r][1], up[1], dn[1], mid[r][0], right, mid[r][1]);
         }
     };
-    auto store_level = [&](int l, const V (&pl)[PY]) {
+    auto store_level = [&](int l, int buf, const V (&pl)[PY]) {
 #pragma unroll
         for (int r = 0; r < PY; r++) {
-            lds[image_index(l, r, 0, me)] = pl[r][0];
-            lds[image_index(l, r, 1, me)] = pl[r][1];
-        }
-    };
-
-    // the same for images 1 and 2, in the buffer at `base` (cur or oth)
-    auto fetch_alt = [&](int l, LT *base, T (&nb)[READ_KINDS]) {
-        LT *const b = base + me, *const b2 = base + me2;
-#pragma unroll
-        for (int k = 0; k < READ_KINDS; k++) {
-            const bool second = k == RD_BELOW1 || k == RD_LEFT1 || k == RD_RIGHT0 || k == RD_RIGHT1;
-            nb[k] = (second ? b2 : b)[alt_read_index(l, k, 0)];
-        }
-    };
-    auto store_alt = [&](int l, LT *base, const V (&pl)[PY]) {
-        LT *const b = base + me;
-#pragma unroll
-        for (int r = 0; r < PY; r++) {
-            b[alt_index(l, r, 0, 0)] = pl[r][0];
-            b[alt_index(l, r, 1, 0)] = pl[r][1];
+            if (buf) {
+                alt[alt_index(l, r, 0, me)] = pl[r][0];
+                alt[alt_index(l, r, 1, me)] = pl[r][1];
+            } else {
+                lds[image_index(l, r, 0, me)] = pl[r][0];
+                lds[image_index(l, r, 1, me)] = pl[r][1];
+            }
         }
     };
 
     // R[L][s]: level L, plane slot s; slot of local plane j = j mod 3
-    V R[LEVELS][3][PY], pre[PY];
+    V R[LEVELS][3][PY];
 #pragma unroll
     for (int l = 0; l < LEVELS; l++)
 #pragma unroll
@@ -183,65 +199,111 @@ __global__ void __launch_bounds__(e4plan::THREADS) euler4_kernel(const LapArgs a
     load_plane(1, R[0][1]);
     load_plane(2, R[0][2]);
 #pragma unroll
-    for (int l = 0; l < LEVELS; l++) store_level(l, R[l][(4 - l) % 3]);   // the middle planes of iteration 0 (level 0: plane 1; the others: zeros)
+    for (int l = 0; l < LEVELS; l++) store_level(l, 0, R[l][(4 - l) % 3]);   // the middle planes of iteration 0 (level 0: plane 1; the others: zeros)
     __syncthreads();
 
-    // iteration i, i mod 3 == K: level 0 holds planes i, i + 1, i + 2 in slots K, K + 1, K + 2 (mod 3); level L the planes L lower.
-    // The order of the LDS traffic and the two barriers is e4plan::SCHEDULE.
-    auto phase = [&](int i, auto kc) {
-        constexpr int K = decltype(kc)::value;
-        load_plane(i + 3, pre);   // needed at the next iteration
+    // iteration i, i mod 3 == K, i mod 2 == P: level 0 holds planes i, i + 1, i + 2 in slots K, K + 1, K + 2 (mod 3); level L the planes L
+    // lower; images 1 and 2 are read in their buffers P and written in their buffers 1 - P.  The order of the LDS traffic and the two
+    // barriers is e4plan::SCHEDULE.  A phase executes fp64 arithmetic, LDS and memory instructions and nothing per lane besides: the plane
+    // that is loaded goes straight into the slot of the plane that dies (what level 0 still needs of that one, old - 2 * mid, is taken
+    // first), so the rotation of the slots is a renaming over three phases, the parity one over two, and the loop is unrolled six times.
+    //
+    // Dead lanes masked.  Inside the halo waves 8 ... 10 a lane's patch is not needed at every level its wave executes (e4plan::lane_levels:
+    // the ring-0 lanes of wave 8 and of waves 9 and 10 at levels 2 and 3; the spare lanes of waves 9 and 10, which repeat patches of the other
+    // wave, at every level): 232 of the 2688 lane-levels of a phase.  In those waves the work of level `level` - neighbour reads, arithmetic,
+    // image stores; for the repeated patches level 0's image stores too - runs in the lanes that need it alone; in the owner waves and in
+    // wave 11 the condition is true in every lane.  The compiler folds the two cases into one lane mask per level, loop-invariant and held
+    // in scalar registers, so a section costs every wave three scalar instructions and no vector one.  The plane loads stay outside: every
+    // lane loads (a load inside a branch makes the wait for the plane loaded a phase ago drain the one just issued).  No barrier stands
+    // inside a section.
+    const int mylevels = lane_levels((int)threadIdx.x);
+    const bool masked = wave >= OWNER_WAVES && wave < WAVES - 1;
+    auto lanes = [&](int level, auto work) {
+        if (masked) {
+            if (level <= mylevels) work();
+        } else
+            work();
+    };
+    auto phase = [&](int i, auto kc, auto pc) {
+        constexpr int K = decltype(kc)::value, P = decltype(pc)::value;
+        // (The offsets pass through an empty asm once per phase.  Without it their zero-extension is hoisted out of the loop, a register
+        // pair per row, and every load and store adds 64 bits per lane again instead of taking the scalar base.)
+#pragma unroll
+        for (int r = 0; r < PY; r++) asm volatile("" : "+v"(roff[r]));
+        V d0[PY];
+        minus_twice(R[0][K], R[0][(K + 1) % 3], d0);
+        load_plane(i + 3, R[0][K]);   // plane i is dead: plane i + 3, needed at the next iteration, takes its slot
         // level 3's middle plane of THIS iteration, computed by l = 2 of the one before (iteration 0: the prologue's zeros once more)
-        if (LEVELS - 1 <= nlev) store_level(LEVELS - 1, R[LEVELS - 1][(K + 1) % 3]);
+        if (LEVELS - 1 <= nlev) lanes(LEVELS - 1, [&] { store_level(LEVELS - 1, 0, R[LEVELS - 1][(K + 1) % 3]); });
 #pragma unroll
         for (int l = 0; l < LEVELS; l++) {
             // level l holds planes (i - l, i + 1 - l, i + 2 - l); level l + 1 gets plane i + 1 - l, in the slot of its plane i - 2 - l
             const V (&old)[PY] = R[l][(K + 3 - l) % 3];
             const V (&mid)[PY] = R[l][(K + 4 - l) % 3];
             const V (&nw)[PY] = R[l][(K + 5 - l) % 3];
-            if (l == 0 || l < nlev) {   // level l + 1 is one of the wave's (every wave executes level 1)
+            auto up = [&] {
                 T nb[READ_KINDS];
-                if (l == 0 || l == LEVELS - 1) fetch(l, nb);
-                else fetch_alt(l, cur[l - 1], nb);
+                fetch(l, (l == 0 || l == LEVELS - 1) ? 0 : P, nb);
+                V d[PY];
+                if (l > 0) minus_twice(old, mid, d);
                 if (l < LEVELS - 1) {
                     V (&res)[PY] = R[l + 1][(K + 4 - l) % 3];
-                    level(old, mid, nw, nb, res);
+                    level(l == 0 ? d0 : d, mid, nw, nb, res);
                     // the middle plane of level l + 1 at the next iteration, into the buffer nobody reads in this phase (level 3: kept in
                     // its registers until barrier B has passed)
-                    if (l + 1 < LEVELS - 1) store_alt(l + 1, oth[l], res);
+                    if (l + 1 < LEVELS - 1) store_level(l + 1, 1 - P, res);
                 } else {                // (owner waves only: nlev == LEVELS)
                     V res[PY];
-                    level(old, mid, nw, nb, res);
+                    level(d, mid, nw, nb, res);
                     const int q = i - 2;   // the local plane of level 4: output plane x0 + q - HALO
                     if (owner && q >= HALO) {
-                        const long po = (x0 + q - HALO) * a.p0;
+                        char *const base = out + (x0 + q - HALO) * a.p0 * (long)sizeof(T);   // wave-uniform
 #pragma unroll
-                        for (int r = 0; r < PY; r++) __builtin_nontemporal_store(res[r], (V *)(out + po + roff[r]));
+                        for (int r = 0; r < PY; r++) {
+                            asm volatile("" : "+v"(soff[r]));   // (as above, in the block of the stores)
+                            __builtin_nontemporal_store(res[r], (V *)(base + soff[r]));
+                        }
                     }
                 }
-            }
+            };
+            if (l == LEVELS - 1) {
+                if (l < nlev) up();     // (owner waves only: no lane of theirs is masked)
+            } else if (l == 0 || l < nlev)
+                lanes(l + 1, up);       // level l + 1 is one of the wave's (every wave executes level 1)
             if (l == 0) {
                 __syncthreads();        // A: every wave has read the image of level 0 ...
-                store_level(0, nw);     // ... plane i + 2 takes its place
+                lanes(1, [&] { store_level(0, 0, nw); });   // ... plane i + 2 takes its place
             }
         }
-        __syncthreads();                // B: every wave has read the image of level 3 (and the buffers `cur` of levels 1 and 2)
-#pragma unroll
-        for (int r = 0; r < PY; r++) R[0][K][r] = pre[r];   // plane i is dead: plane i + 3 takes its slot
-#pragma unroll
-        for (int b = 0; b < ALT_LEVELS; b++) {
-            LT *const t = cur[b];
-            cur[b] = oth[b];
-            oth[b] = t;
-        }
+        __syncthreads();                // B: every wave has read the image of level 3 (and the buffers P of levels 1 and 2)
     };
-    const int iend = lx + 2 * HALO - 3;   // the last iteration: level 4 at plane lx + HALO - 1
-    for (int i = 0;; i += 3) {
-        phase(i, std::integral_constant<int, 0>());
-        if (i + 1 > iend) break;
-        phase(i + 1, std::integral_constant<int, 1>());
-        if (i + 2 > iend) break;
-        phase(i + 2, std::integral_constant<int, 2>());
-        if (i + 3 > iend) break;
+    // One exit: whole rounds of six phases, then the phases left over (at most five), which go on where a round would.  The trip counts
+    // depend on the workgroup alone.
+    const int nphases = lx + 2 * HALO - 2;   // the last iteration computes level 4 at plane lx + HALO - 1
+    typedef std::integral_constant<int, 0> C0;
+    typedef std::integral_constant<int, 1> C1;
+    typedef std::integral_constant<int, 2> C2;
+    int i = 0;
+    for (; i + 6 <= nphases; i += 6) {
+        phase(i, C0(), C0());
+        phase(i + 1, C1(), C1());
+        phase(i + 2, C2(), C0());
+        phase(i + 3, C0(), C1());
+        phase(i + 4, C1(), C0());
+        phase(i + 5, C2(), C1());
+    }
+    const int left = nphases - i;
+    if (left > 0) {
+        phase(i, C0(), C0());
+        if (left > 1) {
+            phase(i + 1, C1(), C1());
+            if (left > 2) {
+                phase(i + 2, C2(), C0());
+                if (left > 3) {
+                    phase(i + 3, C0(), C1());
+                    if (left > 4) phase(i + 4, C1(), C0());
+                }
+            }
+        }
     }
 }
