@@ -1079,6 +1079,59 @@ int pdehip_domain_properties(const pdehip_grid_t *g, const void *arr_full, const
                              const int *periodic_host, double absmax, int32_t *anchor_dev, int64_t *moment_dev, int32_t *box_dev,
                              int64_t *limb_dev, uint32_t *excluded_dev, void *stream);
 
+/* ---- the spectrum of a field where it lives: forward transform and sums of the power over shells of |k| (optional entry points; the
+ * ABI version stays 8) -------------------------------------------------------------------------------------------------------------------
+ * What `np.fft.fftn(state.data)` followed by a radial average in a tracker callback answers, without moving the state to the host.  All
+ * three read the INTERIOR cells of real full arrays in the device layout (fp64 or fp32, 1-D to 3-D; ghost cells and row padding never
+ * enter, the input is never written).  Axes are normalised to three (an n-D grid has the trailing n; a missing axis has one cell); n_a is
+ * the interior extent of axis a and nh = n_2 / 2 + 1.
+ *
+ * pdehip_fft_supported: 0 where every axis of g has a power-of-two extent, at most 1024 cells and at most 4096 on the fastest axis (an
+ * extent of 1 counts as an absent axis); else PDEHIP_E_NOTIMPL with the axis and its extent named in pdehip_last_error.  Nothing is
+ * launched.  The other two entries refuse the same grids the same way.
+ *
+ * pdehip_fft_forward: spectrum_dev receives the unnormalised forward transform F(m) = sum_x f(x) exp(-2 pi i m.x / n) of every
+ * component as complex128 in C order (ncomp, n_0, n_1, nh) - the Hermitian half `np.fft.rfftn` returns.  Both field types are transformed
+ * in fp64; an fp32 element is converted exactly at the load.  Every line, whatever its extent N, goes through ONE schedule in LDS: the
+ * elements are stored bit-reversed, then stage s = 1 ... log2(N) replaces the pair (u, v) = (x[i], x[i + h]), h = 2^(s - 1),
+ * i = (t >> (s - 1) << s) + k, k = t mod h, for t = 0 ... N / 2 - 1 by (u + p, u - p), where p = w v = (ac - bd) + i (ad + bc) for
+ * w = a + i b = W[k N / 2^s] and v = c + i d, every operation rounded once (no FMA contraction in any build).  W[m] = exp(-2 pi i m / N),
+ * 0 <= m < N / 2, is a table made on the host from cos and sin of an angle in the first octant; nothing on the device evaluates a
+ * trigonometric function.  The fastest axis is transformed first, each row as a complex line with zero imaginary parts of which the
+ * first nh outputs are kept, then axis 1 and axis 0 of the half spectrum in place, in tiles of at least 8 neighbouring columns (128
+ * contiguous bytes per line index; the tile at the end of the columns is ragged).  An output is a fixed expression of the inputs: it
+ * has the same bits however the butterflies are spread over lanes, waves and workgroups, and a serial host version gives equal bits.
+ * A line takes 16 N bytes of LDS and its table 8 N: at most 96 KiB for a row of 4096 cells, 136 KiB for a tile of lines of 1024.
+ *
+ * pdehip_shell_spectrum: kfreq_dev holds the frequencies of the axes of g one after the other (sum of the extents; the caller uploads
+ * `np.fft.fftfreq(n_a, dx_a)`), edges_dev nbins + 1 finite fp64 edges e[0] < ... < e[nbins], 1 <= nbins <= 4096.  Mode (i, j, k) of the
+ * half spectrum, k < nh, has |k| = sqrt((f_0[i]^2 + f_1[j]^2) + f_2[k]^2) in that order (a missing axis contributes 0), falls into slot
+ * b with e[b] <= |k| < e[b + 1] (the last bin closed; slot nbins: below e[0], slot nbins + 1: above e[nbins] - pdehip_histogram's rule),
+ * has the weight 2 for 0 < k < n_2 / 2 and 1 otherwise (its mirror image is not stored), and the weighted power
+ * v = weight * (re * re + im * im).
+ *     counts_dev[b], b < nbins + 2            uint64: the sum of the weights, i.e. the modes of the FULL spectrum in the slot; the same
+ *                                             for all components; the sum over the slots is the number of interior cells
+ *     sums_dev[c * (nbins + 2) + b]           fp64: the sum of v over the slot for component c
+ * A sum does not depend on the order of the modes.  A first sweep takes count and the largest v of every slot (integer maximum of the
+ * bit image).  With E the exponent frexp returns for that maximum, L = ceil(log2(count)), D = 63 - L, eh = E - (62 - L), em = eh - D and
+ * el = em - D, a second sweep adds for every mode the three integers hi = rint(ldexp(v, -eh)), mid = rint(ldexp(r, -em)) with
+ * r = v - ldexp(hi, eh) (exact) and lo = rint(ldexp(r', -el)) with r' = r - ldexp(mid, em) (exact): |hi|, |mid|, |lo| <= 2^(62 - L), so
+ * no 64-bit sum of up to 2^L of them overflows, and the three sums hold the sum of v within count * 2^(el - 1), which is below
+ * 2^(4 L - 188) of the sum itself.  Lanes of a wave that meet the same slot are combined first, workgroups add in LDS and fold with
+ * 64-bit integer atomics: no floating-point atomic anywhere.  The limbs are read back and converted on the host - carried into three
+ * non-negative digits, the leading 64 bits and a sticky bit rounded ONCE to nearest - and the sums are written to sums_dev; the call
+ * waits for the stream twice (edges, limbs).  A slot whose maximum is zero, infinite or NaN gets that maximum as its sum.
+ * With several components the transform of each reuses one spectrum buffer.  Spectrum, tables, maxima and limbs are kept per stream,
+ * grown on demand and freed by pdehip_release_scratch.  pdehip_last_kernel_name gives the chain of the instances launched for the last
+ * component, joined by '+'.
+ *
+ * Refused (status PDEHIP_E_VALUE, message in pdehip_last_error): NULL pointers, ncomp outside 1 ... 64, nbins outside 1 ... 4096, edges
+ * that are not finite or not strictly increasing, a misaligned array (16 bytes for the field and the spectrum, 8 for the others). */
+int pdehip_fft_supported(const pdehip_grid_t *g);
+int pdehip_fft_forward(const pdehip_grid_t *g, int ncomp, const void *arr_full, void *spectrum_dev, void *stream);
+int pdehip_shell_spectrum(const pdehip_grid_t *g, int ncomp, const void *arr_full, const double *kfreq_dev, int nbins,
+                          const double *edges_dev, uint64_t *counts_dev, double *sums_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

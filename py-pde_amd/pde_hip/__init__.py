@@ -27,6 +27,7 @@ from .pdes import (PDE, AllenCahnPDE, CahnHilliardPDE, DiffusionPDE, KleinGordon
 from .poisson import solve_laplace_equation, solve_poisson_equation
 from .projection import image_data, line_data, project, slice_field
 from .smoothing import smooth
+from .spectrum import FieldSpectrum, field_spectrum
 from .statistics import FieldStatistics, field_statistics
 from .solvers import Controller, ConvergenceError, CrankNicolsonSolver, EulerSolver, ExplicitSolver, ImplicitSolver, RungeKuttaSolver
 
@@ -52,6 +53,7 @@ __all__ = [
     "ExplicitSolver",
     "FieldDomains",
     "FieldHistogram",
+    "FieldSpectrum",
     "FieldStatistics",
     "HipBackend",
     "ImplicitSolver",
@@ -65,6 +67,7 @@ __all__ = [
     "field_histogram",
     "field_median",
     "field_quantile",
+    "field_spectrum",
     "field_statistics",
     "get_backend",
     "image_data",

@@ -381,6 +381,10 @@ OPTIONAL_PROTOTYPES: dict[str, list] = {
     "domain_sizes": [_vp, _i64, _i64, _vp, _vp],
     # anchors, offset sums, boxes and fixed-point field sums of labelled domains (csrc/pdehip_props.hip)
     "domain_properties": [_pg, _vp, _vp, _i64, C.POINTER(_i), _d, _vp, _vp, _vp, _vp, _vp, _vp],
+    # forward transform into a dense half spectrum and the sums of its power over shells of |k| (csrc/pdehip_fft.hip)
+    "fft_supported": [_pg],
+    "fft_forward": [_pg, _i, _vp, _vp, _vp],
+    "shell_spectrum": [_pg, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp],
 }
 
 PROJECT_SUM, PROJECT_MAX, PROJECT_MIN = 0, 1, 2

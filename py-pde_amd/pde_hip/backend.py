@@ -63,9 +63,10 @@ from .projection import ProjectionMixin  # noqa: E402
 from .smoothing import SmoothingMixin  # noqa: E402
 from .distribution import DistributionMixin  # noqa: E402
 from .domains import DomainsMixin  # noqa: E402
+from .spectrum import SpectrumMixin  # noqa: E402
 
 
-class HipBackendMixin(OperatorGlueMixin, InterpolationMixin, StatisticsMixin, ProjectionMixin, SmoothingMixin, DistributionMixin, DomainsMixin, RhsPlanningMixin, NoiseHookMixin, StepperMixin):
+class HipBackendMixin(OperatorGlueMixin, InterpolationMixin, StatisticsMixin, ProjectionMixin, SmoothingMixin, DistributionMixin, DomainsMixin, SpectrumMixin, RhsPlanningMixin, NoiseHookMixin, StepperMixin):
     """Implementation shared by the stand-alone and the py-pde-plugin backend classes."""
 
     implementation = "hip"
