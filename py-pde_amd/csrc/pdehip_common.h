@@ -145,6 +145,7 @@ inline bool stage_aligned(const LapArgs &a)
     return bits % 16 == 0;
 }
 void note_kernel(const char *fmt, ...);   // pdehip_runtime.hip: name of the kernel instance launched last (pdehip_last_kernel_name)
+void note_kernel_text(const char *name);  // the same for a name the caller keeps ready (no formatting per launch)
 // StageFuse (what follows a slope k = dt*rhs in a Runge-Kutta scheme, fused into the sweep that computes k): pdehip_slab_loops.h
 // launch configuration of the two-level kernel handed to a caller that launches a run-time compiled instance itself
 struct Euler2Plan {

@@ -18,6 +18,7 @@
 #include "pdehip_common.h"
 #include "pdehip_rk_loops.h"
 #include "pdehip_fixedpoint.h"
+#include "pdehip_jit_plan.h"
 #include "pdehip_sources.h"   // generated: kDeviceH, kMarchInc (raw string literals)
 
 using namespace pdehip;
@@ -291,6 +292,34 @@ int pdehip_jit_destroy(void *handle)
 }  // extern "C"
 
 namespace {
+// PDEHIP_JIT_RY / _CZ / _WY / _BLOCKS (tuning aids, pdehip_jit_plan.h), read once per process
+const jitplan::Knobs &jit_knobs()
+{
+    static const jitplan::Knobs k = jitplan::knobs_from_env();
+    return k;
+}
+
+// pdehip_last_kernel_name of a one-level launch.  The launch-bound loops repeat a few (kernel, geometry) pairs thousands of times: the name is
+// formatted when a pair is first seen by the thread and costs one comparison per launch afterwards.
+struct NotedLaunch {
+    hipFunction_t fn = nullptr;
+    long lx = 0, nxc = 0, nblocks = 0;
+    char name[192];
+};
+void note_launch(hipFunction_t fn, const jitplan::Choice &c)
+{
+    constexpr int kSlots = 8;
+    static thread_local NotedLaunch slots[kSlots];
+    static thread_local unsigned next = 0;
+    for (const NotedLaunch &s : slots)
+        if (s.fn == fn && s.lx == c.lx && s.nxc == c.nxc && s.nblocks == c.nblocks) { note_kernel_text(s.name); return; }
+    NotedLaunch &s = slots[next++ % kSlots];
+    s.fn = fn; s.lx = c.lx; s.nxc = c.nxc; s.nblocks = c.nblocks;
+    jitplan::format_name(c, s.name, sizeof(s.name) - 32);
+    if (fastmath_on()) strcat(s.name, " [fastmath: FMA contraction]");   // (the exact and the contracted build are different functions)
+    note_kernel_text(s.name);
+}
+
 // stage != NULL: the generated epilogue is the slope of a Runge-Kutta stage and the combination that follows it is
 // computed in the same sweep (StageFuse, pdehip_common.h); *done = 0 and nothing launched when the vectorised kernel
 // does not cover the grid (the caller then runs pdehip_jit_apply + lincomb / combine)
@@ -305,7 +334,6 @@ int jit_apply_impl(void *handle, const pdehip_grid_t *g, void *in_full, const vo
     NGrid n;
     PDEHIP_TRY(norm_grid(g, &n));
     const bool f64 = n.dtype == PDEHIP_F64;
-    const int vec = f64 ? 2 : 4;
     const OutStr o = out_strides(n, PDEHIP_OUT_FULL);
     LapArgs a;
     memset(&a, 0, sizeof(a));
@@ -337,7 +365,7 @@ int jit_apply_impl(void *handle, const pdehip_grid_t *g, void *in_full, const vo
         for (int m = 0; m < 5; m++) bits |= (uintptr_t)a.st_k[m];
         aligned = aligned && bits % 16 == 0;
     }
-    const bool fast = n.ndim >= 2 && aligned;   // any row length: rows ending inside a vector are stored element-wise (pdehip_march.inc)
+    const bool fast = jitplan::vectorised(n.ndim, aligned);   // any row length: rows ending inside a vector are stored element-wise (pdehip_march.inc)
     if (stage && !fast) return 0;   // only the vectorised kernel carries the stage epilogue
 
     // boundary conditions: on the fly where possible (fast kernel), ghost kernel otherwise
@@ -372,68 +400,34 @@ int jit_apply_impl(void *handle, const pdehip_grid_t *g, void *in_full, const vo
     a.any_ibc = n_fused > 0;
 
     Variant v;
-    unsigned blocks, threads;
     const char *tname = f64 ? "double" : "float";
-    if (fast) {
-        const long chunks = (n.n[2] + 64L * vec - 1) / (64L * vec);
-        int cz = chunks >= 4 ? 4 : (chunks >= 2 ? 2 : 1);
-        int ry = 2;   // measured: 2-row tiles win in 2-D as well (4096^2 Allen-Cahn 80 % vs 40 % of the HBM peak with 8 rows)
-        static int ry_env = -1;   // PDEHIP_JIT_RY: rows per wave tile (tuning aid; any value works, kernels are built on demand)
-        if (ry_env < 0) { const char *e = getenv("PDEHIP_JIT_RY"); ry_env = e ? atoi(e) : 0; }
-        // stage sweeps: 1-row tiles.  The 2-row stage kernel (28 KB of code) runs at its one-wave-per-SIMD speed when it
-        // is loaded through hipModuleLoadData (4.9 vs 3.7 ms per RK4 step at 512^3; the same code built into the library
-        // is not affected, nor is this one once librocprofiler-sdk.so is in the process); with half the code the
-        // effect is gone (4.0 ms): profiles/r01_time_expr_rk.md
-        if (stage) ry = 1;
-        if (ry_env > 0) ry = ry_env;
-        static int cz_env = -1;   // PDEHIP_JIT_CZ: chunks per wave tile (tuning aid)
-        if (cz_env < 0) { const char *e = getenv("PDEHIP_JIT_CZ"); cz_env = e ? atoi(e) : 0; }
-        if (cz_env > 0 && cz_env <= cz) cz = cz_env;
-        auto n_tiles = [&](int ry_, int cz_) {
-            const long per_plane = ((n.n[1] + ry_ - 1) / ry_) * ((n.n[2] + 64L * vec * cz_ - 1) / (64L * vec * cz_));
-            return n.ndim == 3 ? per_plane * n.n[0] : per_plane;
-        };
-        while (cz > 1 && n_tiles(ry, cz) < 512) cz /= 2;
-        const bool hasx = n.ndim == 3, ibc = n_fused > 0;
-        static int wy_env = -1;   // PDEHIP_JIT_WY: waves per workgroup of the stage sweeps (tuning aid)
-        if (wy_env < 0) { const char *e = getenv("PDEHIP_JIT_WY"); wy_env = e ? atoi(e) : 0; }
-        const int wy = (stage && wy_env > 0) ? wy_env : 1;
-        const bool tails = (n.n[2] % vec != 0) || (chunks % cz != 0);
-        const std::string key = std::string(tname) + "," + std::to_string(ry) + "," + std::to_string(cz) + "," + (hasx ? "x" : "-") + (ibc ? "b" : "-") +
-                                (stage ? "s" : "-") + std::to_string(wy) + (tails ? "t" : "-");
+    jitplan::Query q;
+    q.elem = f64 ? 8 : 4; q.ndim = n.ndim; q.n0 = n.n[0]; q.n1 = n.n[1]; q.n2 = n.n[2];
+    q.aligned = aligned; q.stage = stage != nullptr; q.kind = stage ? stage->kind : 0;
+    q.nk = !stage ? 0 : (stage->k[1] ? 2 : (stage->k[0] ? 1 : 0));
+    q.fused = n_fused > 0;
+    const jitplan::Choice c = jitplan::plan(q, jit_knobs());
+    if (!c.generic) {
+        const std::string key = std::string(tname) + "," + std::to_string(c.ry) + "," + std::to_string(c.cz) + "," + (c.hasx ? "x" : "-") + (c.ibc ? "b" : "-") +
+                                (c.stage ? "s" : "-") + std::to_string(c.wy) + (c.tails ? "t" : "-");
         auto it = j->cache.find(mode_key(key));
         if (it != j->cache.end()) v = it->second;
-        else PDEHIP_TRY(compile_variant(j, key, false, tname, vec, ry, cz, hasx, ibc, &v, 0, stage != nullptr, wy, tails));
-        a.ntz = (a.n2 + 64L * vec * cz - 1) / (64L * vec * cz);
-        a.nty = (a.n1 + wy * ry - 1) / (wy * ry);
-        const long tiles = a.ntz * a.nty;
-        long lx = a.n0;
-        if (hasx) {
-            // stages with few pointwise streams: two waves per SIMD (see launch_laplace_t, profiles/r01_time_rk.md)
-            static long want_env = -1;   // PDEHIP_JIT_BLOCKS: wave tiles per sweep (tuning aid)
-            if (want_env < 0) { const char *e = getenv("PDEHIP_JIT_BLOCKS"); want_env = e ? atol(e) : 0; }
-            const long want = want_env > 0 ? want_env : ((stage && (stage->kind == 1 || !stage->k[1])) ? 2048 : 1024);
-            long nxc = (want / wy + tiles - 1) / tiles;   // `want` counts waves
-            if (nxc < 1) nxc = 1;
-            if (nxc > a.n0) nxc = a.n0;
-            lx = (a.n0 + nxc - 1) / nxc;
-        }
-        a.lx = (int)lx;
-        a.nxc = (a.n0 + lx - 1) / lx;
-        a.nblocks = a.nxc * tiles;
-        blocks = (unsigned)a.nblocks;
-        threads = 64 * wy;
+        else PDEHIP_TRY(compile_variant(j, key, false, tname, c.vec, c.ry, c.cz, c.hasx, c.ibc, &v, 0, c.stage, c.wy, c.tails));
+        a.ntz = c.ntz;
+        a.nty = c.nty;
+        a.lx = (int)c.lx;
+        a.nxc = c.nxc;
+        a.nblocks = c.nblocks;
     } else {
         const std::string key = std::string("generic,") + tname;
         auto it = j->cache.find(mode_key(key));
         if (it != j->cache.end()) v = it->second;
         else PDEHIP_TRY(compile_variant(j, key, true, tname, 1, 1, 1, false, false, &v));
-        long b = (n.n[0] * n.n[1] * n.n[2] + 255) / 256;
-        blocks = (unsigned)(b > 8192 ? 8192 : (b < 1 ? 1 : b));
-        threads = 256;
     }
+    const unsigned blocks = (unsigned)c.nblocks, threads = c.threads;
     void *args[] = {&a};
     PDEHIP_HIP(hipModuleLaunchKernel(v.fn, blocks, 1, 1, threads, 1, 1, 0, as_stream(stream), args, nullptr));
+    note_launch(v.fn, c);
     if (done) *done = 1;
     return 0;
 }
@@ -518,6 +512,7 @@ int pdehip_jit_euler2(void *handle, const pdehip_grid_t *g, const void *in_full,
     else PDEHIP_TRY(compile_variant(j, key, false, tname, f64 ? 2 : 4, plan.ry, 1, plan.has_y, true, &v, E2_CUSTOM));
     void *kargs[] = {&plan.a};
     PDEHIP_HIP(hipModuleLaunchKernel(v.fn, plan.grid, 1, 1, plan.block, 1, 1, 0, as_stream(stream), kargs, nullptr));
+    note_kernel("pde_kernel<two,%s,%d,RY=%d,%s> (two applications of the epilogue per sweep; run-time built)", tname, f64 ? 2 : 4, plan.ry, plan.has_y ? "3-D" : "2-D");
     *done = 1;
     return 0;
 }
@@ -563,6 +558,7 @@ int pdehip_jit_fused2(void *handle, const pdehip_grid_t *g, const void *in_full,
     else PDEHIP_TRY(compile_variant(j, key, false, tname, f64 ? 2 : 4, plan.ry, 1, plan.has_y, true, &v, E2_CUSTOM2));
     void *kargs[] = {&plan.a};
     PDEHIP_HIP(hipModuleLaunchKernel(v.fn, plan.grid, 1, 1, plan.block, 1, 1, 0, as_stream(stream), kargs, nullptr));
+    note_kernel("pde_kernel<fused2,%s,%d,RY=%d,%s> (both passes of the expression in one sweep; run-time built)", tname, f64 ? 2 : 4, plan.ry, plan.has_y ? "3-D" : "2-D");
     *done = 1;
     return 0;
 }
@@ -1087,7 +1083,7 @@ struct JitEval {
         again.exchange = nullptr;   // (its operand has just been exchanged)
         return run_passes(g, &again, 1, fixed, (char *)in, (char *)k_out, comp_bytes, params, st);
     }
-    const char *sweep_name() const { return "pde_kernel (run-time build of lap_march_body, LAP_CUSTOM with the stage epilogue)"; }
+    const char *sweep_name() const { return nullptr; }   // (jit_apply_impl has noted the instance)
     // One fixed-point iteration (StageFuse kind 5, pdehip_fixedpoint.h): every pass but the last as usual, the last one with the update and
     // the convergence norm in its sweep where it runs on the vectorised kernel; else (systems, 1-D, generic kernel) the slope into
     // `k_out` and the caller's pointwise kernel.  sf->k[1] is the iterate the passes start from.

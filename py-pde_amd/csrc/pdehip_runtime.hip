@@ -18,6 +18,11 @@ void note_kernel(const char *fmt, ...)
     va_end(ap);
     if (fastmath_on() && len > 0 && len < (int)sizeof(g_last_kernel) - 40) snprintf(g_last_kernel + len, sizeof(g_last_kernel) - len, " [fastmath: FMA contraction]");
 }
+// a name formatted once by the caller (fastmath suffix included): launch-bound loops pay one comparison per launch
+void note_kernel_text(const char *name)
+{
+    if (strcmp(g_last_kernel, name) != 0) snprintf(g_last_kernel, sizeof(g_last_kernel), "%s", name);
+}
 }  // namespace pdehip
 
 using namespace pdehip;

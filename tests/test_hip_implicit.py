@@ -203,6 +203,18 @@ def test_expression_diffusion_takes_the_epilogue_in_its_pass(backend):
         assert sol.info["iterations"] == counts and sol.info["function_evaluations"] == evals
         assert np.array_equal(res.data, want)
         assert "fixed-point epilogue" in name, name
+        # the host recognises ``D * laplace(c)`` as the diffusion equation: the iterations ran on the built-in stage sweep
+        assert name.startswith("lap_march_kernel<double,2,") and "mode=10" in name, name
+        # with a decay term the expression compiler takes it: the run-time built stage instance of this grid (one row per tile, the wall
+        # applied on the fly), the same epilogue in its pass, the same bits as the restatement
+        decay = pde_hip.PDE({"c": "0.7 * laplace(c) - 0.5 * c"}, bc=["periodic", {"value": 0.4}, "periodic"])
+        res, sol = solve(decay, state.copy(), 0.05, 3, solver, backend, **kw)
+        name = _lib.get_lib().last_kernel_name().decode()
+        diffusion = oracle_rhs(grid, twin)
+        want, evals, counts = fixedpoint_run(lambda valid, t: diffusion(valid, t) - 0.5 * valid, state.data, 0.05, 3, scheme=solver, **kw)
+        assert sol.info["iterations"] == counts and sol.info["function_evaluations"] == evals
+        assert np.array_equal(res.data, want)
+        assert name.startswith("pde_kernel<double,2,RY=1,CZ=1,WY=1,3-D,ibc,stage,-> (lx=1, 12 x-chunks; run-time built) + fixed-point epilogue"), name
 
 
 @pytest.mark.parametrize("shape", [(12, 12, 32), (128, 128, 128), (40, 64), (96,)])
