@@ -1132,6 +1132,48 @@ int pdehip_fft_forward(const pdehip_grid_t *g, int ncomp, const void *arr_full, 
 int pdehip_shell_spectrum(const pdehip_grid_t *g, int ncomp, const void *arr_full, const double *kfreq_dev, int nbins,
                           const double *edges_dev, uint64_t *counts_dev, double *sums_dev, void *stream);
 
+/* ---- the inverse transform, and Poisson's equation on all-periodic grids solved by it (optional entry points; the ABI version stays 8) -------
+ * pdehip_fft_inverse: spectrum_dev is the dense half spectrum (ncomp, n_0, n_1, nh) pdehip_fft_forward writes; out_full, a full array of g
+ * (fp64 or fp32), receives in its INTERIOR cells f(x) = Re sum_m F(m) exp(+2 pi i m.x / n) / size, size = n_0 n_1 n_2 (a power of two: the
+ * scaling is exact).  Ghost cells, row padding and slack are not written.  The spectrum is CONSUMED: the slow-axis passes run in place.
+ * Dataflow, fixed like the forward's: axis 0, then axis 1 of the half spectrum (inverse_lines_kernel: tiles, ragged-tile rule and LDS
+ * layout of fft_lines_kernel), then the fastest axis (inverse_rows_kernel<T>); absent axes and axes of extent 1 are skipped.  The
+ * butterflies and their schedule are those of the forward transform with the twiddles W[m] conjugated at the copy of the table into LDS
+ * (a sign flip is exact).  A row becomes a full complex line of N = n_2 elements: element k <= N / 2 is the stored element as it is -
+ * including whatever imaginary part sits at k = 0 and k = N / 2 -, element N - k for 0 < k < N / 2 its conjugate; the line is loaded
+ * bit-reversed, transformed, and the REAL part times 1 / size is stored, rounded once to the type of g; the imaginary part is dropped
+ * (it vanishes for the spectrum of a real field).  max(1, 512 / N) rows per workgroup.  Every output element is a fixed expression of
+ * the spectrum, independent of the lane, wave or workgroup that evaluates it; one rounding per operation; a serial host version gives
+ * equal bits.  LDS as for the forward transform: at most 96 KiB for rows and 136 KiB for lines.  Grid limits, refusals and alignment
+ * checks are those of pdehip_fft_forward.  pdehip_last_kernel_name gives the chain of launches joined by '+'.
+ *
+ * pdehip_poisson_fft: solves A u = f where A is the 3/5/7-point Laplacian of g with periodic wrap on EVERY axis (the caller vouches for
+ * that: the call takes no faces; v = L(0) = 0) and returns the minimum-norm (zero-mean) solution, as the reference's lsmr branch and
+ * pdehip_poisson_solve do for singular systems.  No iteration:
+ *   1. the forward transform of rhs_full (fp64 arithmetic for both field types; rhs_full is not modified) into a scratch spectrum;
+ *   2. fftsolve_divide_kernel over the half spectrum: u^(m) = (f^(m) / mu(m)) * (-1), an IEEE division per part, and u^(0) = 0 exactly
+ *      whatever f^(0) is - that is the projection, no mean is computed or subtracted.  mu(m) = (mu_0[i] + mu_1[j]) + mu_2[k] in that order
+ *      from per-axis host tables mu_a[m] = (4 (s s)) scale_a, s = sin(pi m' / n_a) with the angle 3.14159265358979323846 * m' / n_a,
+ *      m' = min(m, n_a - m), scale_a = 1 / dx_a^2 as the Laplacian kernels use it; an absent axis has the one entry 0.  (The sine form,
+ *      because 2 cos - 2 loses the low modes to cancellation.)
+ *   3. the passes of pdehip_fft_inverse into an fp64 full-layout scratch array x;
+ *   4. the acceptance test pdehip_poisson_solve applies to singular systems: periodic ghost cells of x, w = A x with the stencil
+ *      kernels, then one sweep (fftsolve_check_kernel) whose waves leave their shares of four sums in slots of their own - no
+ *      floating-point atomic; the host adds them in slot order -: the count of cells with !(|w - f| <= 1e-5 + 1e-5 |f|),
+ *      sum (w - f)^2, sum (w - (f - fbar))^2 and sum (f - fbar)^2 with fbar = f^(0) / size read from the spectrum before step 2;
+ *   5. x is stored to out_full, rounded once to the field type (in the sweep of step 4; out_full may be rhs_full).
+ * io: in rtol, atol (maxiter and batch are ignored).  Out: iterations = 0, singular = 1, rhs_norm = ||f - fbar||_2,
+ * residual = ||A x - (f - fbar)||_2 - the TRUE residual, not a recurrence -, check_residual = ||A x - f||_2, and status 2 if a sum is not
+ * finite, else 4 if the count is not zero (an inconsistent right-hand side: the reference's RuntimeError), else 1 if
+ * residual > max(rtol * rhs_norm, atol), else 0.  The attainable residual of ANY fp64 method is about u ||A|| ||x|| (u = 2^-53): a smooth
+ * right-hand side on a 4096-cell 1-D grid can therefore miss an rtol near 1e-10; that is reported (status 1), not hidden.
+ * The eigenvalue tables, the spectrum, x, w and the slots (256 KiB) are kept per stream with the scratch of the transforms and freed by
+ * pdehip_release_scratch.  The call waits for the stream once.  pdehip_last_kernel_name gives the chain of the transform and solve
+ * launches: it ends in "+fftsolve_divide_kernel+<inverse passes>+fftsolve_check_kernel".  Grids are refused as by pdehip_fft_supported;
+ * also refused (PDEHIP_E_VALUE): NULL pointers, arrays not on a 16-byte boundary, rtol or atol negative or NaN. */
+int pdehip_fft_inverse(const pdehip_grid_t *g, int ncomp, void *spectrum_dev, void *out_full, void *stream);
+int pdehip_poisson_fft(const pdehip_grid_t *g, const void *rhs_full, void *out_full, pdehip_poisson_t *io, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,6 +6,10 @@
 //                          the first n2 / 2 + 1 outputs of every line go to the dense half spectrum
 //   fft_lines_kernel       one slower axis of the half spectrum, in place: tiles of at least 8 neighbouring columns (128 bytes) per line
 //                          index, ragged at the end of the columns, because n2 / 2 + 1 is never a multiple of the tile
+//   inverse_lines_kernel   the same tiles with the twiddles conjugated at the copy into LDS (a sign flip is exact): a slower axis of the
+//                          inverse transform, in place
+//   inverse_rows_kernel<T> the fastest axis of the inverse: every stored row of n2 / 2 + 1 elements becomes a full complex line (element
+//                          N - k is the conjugate of element k), the real part of the result times 1 / size goes to the interior cells
 //   shell_max_kernel       per shell the mode count (weight 2 inside the Hermitian half, 1 on its two faces) and the largest weighted
 //                          power as an integer maximum of the bit image
 //   shell_params_kernel    per shell the exponents of three fixed-point limbs from that maximum and the count
@@ -15,21 +19,17 @@
 // w v = (ac - bd) + i (ad + bc), one rounding per operation (no FMA contraction in any build).  An output element is a fixed expression
 // of the inputs: which lane, wave or workgroup evaluates a butterfly does not enter.  Everything that is combined across waves is an
 // integer (counts, maxima of bit images, limbs): no floating-point atomic, two calls give equal bits, a serial host version too.
-#include "pdehip_common.h"
-#include "pdehip_scratch.h"
+#include "pdehip_fft.h"
 #include "pdehip_sweep.h"
 
 namespace pdehip {
 namespace {
 
 constexpr int kShellBinsMax = 4096;
-constexpr long kFftSlowMax = 1024, kFftFastMax = 4096;
 constexpr long kFftBlocksMax = 1024;            // workgroups of a transform pass (each holds 8 KiB or more of LDS)
 constexpr long kShellBlocksMax = 2048;          // workgroups of a shell sweep (each ends with one atomic per shell it met)
 constexpr int kTileMin = 8;                     // columns of a strided tile: 8 complex128 are 128 contiguous bytes per line index
 constexpr long kTileElems = 2048;               // ... and more columns for short lines, up to this many elements (32 KiB) per tile
-
-typedef double2 cplx;
 
 // ---- the twiddle table: exp(-2 pi i m / N), 0 <= m < N / 2, from angles in the first octant (the same lines: tests/shim) -----------------
 void twiddle(long m, long n, double *re, double *im)
@@ -156,6 +156,90 @@ __global__ void __launch_bounds__(256) fft_lines_kernel(LinesArgs a)
         for (int e = threadIdx.x; e < n * tile; e += 256) {
             const int idx = e >> a.log2t, c = e & (tile - 1);
             if (w0 + c < a.width) base[(long)idx * a.width + w0 + c] = x[(long)idx * tile + c];
+        }
+    }
+}
+
+// ---- the inverse: the same butterflies with conjugated twiddles, axis 0, then axis 1, then the fastest axis ---------------------------------
+// LDS, tiles and the ragged-tile rule of fft_lines_kernel
+__global__ void __launch_bounds__(256) inverse_lines_kernel(LinesArgs a)
+{
+    extern __shared__ cplx fft_lds[];
+    const int n = 1 << a.log2n, tile = 1 << a.log2t;
+    cplx *x = fft_lds, *tw = fft_lds + (long)n * tile;
+    for (int i = threadIdx.x; i < n / 2; i += 256) {
+        cplx w = a.tw[i];
+        w.y = -w.y;
+        tw[i] = w;
+    }
+    const long tiles = (a.width + tile - 1) >> a.log2t;
+    const long items = a.outer * tiles;
+    for (long it = blockIdx.x; it < items; it += gridDim.x) {
+        const long o = it / tiles, w0 = (it - o * tiles) << a.log2t;
+        cplx *base = a.spec + o * n * a.width;
+        __syncthreads();
+        for (int e = threadIdx.x; e < n * tile; e += 256) {
+            const int idx = e >> a.log2t, c = e & (tile - 1);
+            cplx v;
+            v.x = 0.0; v.y = 0.0;
+            if (w0 + c < a.width) v = base[(long)idx * a.width + w0 + c];
+            x[(long)bit_reverse((unsigned)idx, a.log2n) * tile + c] = v;
+        }
+        fft_stages(x, tw, a.log2n, tile, a.log2t, tile, 1);
+        for (int e = threadIdx.x; e < n * tile; e += 256) {
+            const int idx = e >> a.log2t, c = e & (tile - 1);
+            if (w0 + c < a.width) base[(long)idx * a.width + w0 + c] = x[(long)idx * tile + c];
+        }
+    }
+}
+
+struct InvRowsArgs {
+    RowGrid g;
+    long pc;                       // elements of one component of the field
+    long rows;                     // n0 * n1
+    int log2n, batch, nh;          // N = n2 = 1 << log2n; rows of one batch; n2 / 2 + 1
+    double inv_size;               // 1 / (n0 n1 n2): a power of two
+    const cplx *in;                // (components, rows, nh)
+    void *out;                     // component 0; workgroup row blockIdx.y takes component blockIdx.y
+    const cplx *tw;                // n2 / 2 twiddles of the forward transform
+};
+
+// LDS: batch * N elements, then N / 2 twiddles
+template <typename T>
+__global__ void __launch_bounds__(256) inverse_rows_kernel(InvRowsArgs a)
+{
+    extern __shared__ cplx fft_lds[];
+    const int n = 1 << a.log2n;
+    cplx *x = fft_lds, *tw = fft_lds + (long)a.batch * n;
+    for (int i = threadIdx.x; i < n / 2; i += 256) {
+        cplx w = a.tw[i];
+        w.y = -w.y;
+        tw[i] = w;
+    }
+    const cplx *in = a.in + (long)blockIdx.y * a.rows * a.nh;
+    T *out = (T *)a.out + (long)blockIdx.y * a.pc;
+    const long batches = (a.rows + a.batch - 1) / a.batch;
+    for (long bt = blockIdx.x; bt < batches; bt += gridDim.x) {
+        __syncthreads();                                       // (the stores of the batch before have read the lines)
+        for (int e = threadIdx.x; e < a.batch * n; e += 256) {
+            const int b = e >> a.log2n, idx = e & (n - 1);
+            const long row = bt * a.batch + b;
+            cplx v;
+            v.x = 0.0; v.y = 0.0;
+            if (row < a.rows) {
+                if (2 * idx <= n) v = in[row * a.nh + idx];                     // stored, with whatever imaginary part sits at 0 and N / 2
+                else { v = in[row * a.nh + (n - idx)]; v.y = -v.y; }             // the mirror image
+            }
+            x[(long)b * n + bit_reverse((unsigned)idx, a.log2n)] = v;
+        }
+        fft_stages(x, tw, a.log2n, a.batch, -1, 1, n);
+        for (int e = threadIdx.x; e < a.batch * n; e += 256) {
+            const int b = e >> a.log2n, k = e & (n - 1);
+            const long row = bt * a.batch + b;
+            if (row < a.rows) {
+                const long i = row / a.g.n1, j = row - i * a.g.n1;
+                out[a.g.off + i * a.g.p0 + j * a.g.p1 + k] = (T)(x[(long)b * n + k].x * a.inv_size);
+            }
         }
     }
 }
@@ -378,25 +462,15 @@ double limbs_to_double(long long lh, long long lm, long long ll, int eh, int L)
     return ldexp((double)(win | (sticky ? 1ULL : 0ULL)), el + s);
 }
 
-// ---- per stream: twiddles, frequencies, the spectrum of one component, maxima, parameters and limbs, pinned host memory -------------------------
-struct FftScratch {
-    cplx *tw_dev, *tw_host;                    // kFftFastMax entries: the tables of axes 0, 1, 2 one after the other
-    long tw_n[3];                              // the extents the tables were made for
-    double *kf_dev;                            // 2 kFftSlowMax + kFftFastMax frequencies of the normalised axes
-    double *edges_host;                        // kShellBinsMax + 1
-    cplx *spec; size_t spec_bytes;
-    unsigned long long *maxbits; int2 *params; long long *limb; size_t slots;          // per (component, slot); params: one component's
-    unsigned long long *host;                  // pinned: maxima, limbs, counts, sums of a call
-    size_t host_slots;
-};
+// ---- per stream (FftScratch, pdehip_fft.h) ----------------------------------------------------------------------------------------------------
 int release_fft();
 StreamTable<FftScratch> g_fft(release_fft);
 
 void free_entry(FftScratch &s)
 {
     (void)hipFree(s.tw_dev); (void)hipFree(s.kf_dev); (void)hipFree(s.spec); (void)hipFree(s.maxbits); (void)hipFree(s.params);
-    (void)hipFree(s.limb);
-    (void)hipHostFree(s.tw_host); (void)hipHostFree(s.edges_host); (void)hipHostFree(s.host);
+    (void)hipFree(s.limb); (void)hipFree(s.mu_dev); (void)hipFree(s.sol_x); (void)hipFree(s.sol_w); (void)hipFree(s.sol_ctl);
+    (void)hipHostFree(s.tw_host); (void)hipHostFree(s.edges_host); (void)hipHostFree(s.host); (void)hipHostFree(s.mu_host); (void)hipHostFree(s.sol_pinned);
     memset(&s, 0, sizeof(s));
 }
 int release_fft() { return g_fft.release(free_entry); }
@@ -422,6 +496,18 @@ int fft_tables(hipStream_t st, const long n[3], const cplx **tw)
     });
 }
 
+int grow_spectrum(FftScratch &s, size_t spec_bytes)
+{
+    if (s.spec_bytes < spec_bytes) {
+        if (s.spec) PDEHIP_HIP(hipFree(s.spec));       // (hipFree waits for the device)
+        s.spec = nullptr; s.spec_bytes = 0;
+        const hipError_t e = hipMalloc((void **)&s.spec, spec_bytes);
+        if (e != hipSuccess) PDEHIP_FAIL(100 + (int)e, "hipMalloc of %zu bytes for the spectrum failed: %s", spec_bytes, hipGetErrorString(e));
+        s.spec_bytes = spec_bytes;
+    }
+    return 0;
+}
+
 int shell_scratch(hipStream_t st, size_t spec_bytes, size_t slots, FftScratch *out)
 {
     return g_fft.with(st, [&](FftScratch &s) -> int {
@@ -430,13 +516,7 @@ int shell_scratch(hipStream_t st, size_t spec_bytes, size_t slots, FftScratch *o
             PDEHIP_HIP(hipHostMalloc((void **)&s.edges_host, sizeof(double) * (kShellBinsMax + 1), hipHostMallocDefault));
             PDEHIP_HIP(hipMalloc((void **)&s.params, sizeof(int2) * (kShellBinsMax + 2)));
         }
-        if (s.spec_bytes < spec_bytes) {
-            if (s.spec) PDEHIP_HIP(hipFree(s.spec));       // (hipFree waits for the device)
-            s.spec = nullptr; s.spec_bytes = 0;
-            const hipError_t e = hipMalloc((void **)&s.spec, spec_bytes);
-            if (e != hipSuccess) PDEHIP_FAIL(100 + (int)e, "hipMalloc of %zu bytes for the spectrum failed: %s", spec_bytes, hipGetErrorString(e));
-            s.spec_bytes = spec_bytes;
-        }
+        PDEHIP_TRY(grow_spectrum(s, spec_bytes));
         if (s.slots < slots) {
             if (s.maxbits) PDEHIP_HIP(hipFree(s.maxbits));
             if (s.limb) PDEHIP_HIP(hipFree(s.limb));
@@ -459,6 +539,10 @@ int log2_of(long n)
     return l;
 }
 
+}  // namespace
+
+StreamTable<FftScratch> &fft_table() { return g_fft; }
+
 // 0, or the refusal of the dry run: every normalised axis absent or a power of two up to 1024, the fastest up to 4096
 int fft_check(const pdehip_grid_t *g, NGrid *n)
 {
@@ -472,12 +556,27 @@ int fft_check(const pdehip_grid_t *g, NGrid *n)
     return 0;
 }
 
+namespace {
+
 // every launch asks for its dynamic LDS: up to 136 KiB of the CU's 160 KiB
 template <class K>
 int allow_lds(K kernel, size_t bytes)
 {
     if (bytes > 65536) PDEHIP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
     return 0;
+}
+
+}  // namespace
+
+namespace fft {
+
+int spectrum_scratch(hipStream_t st, size_t spec_bytes, cplx **spec)
+{
+    return g_fft.with(st, [&](FftScratch &s) -> int {
+        PDEHIP_TRY(grow_spectrum(s, spec_bytes));
+        *spec = s.spec;
+        return 0;
+    });
 }
 
 // the transform of `ncomp` components of `in` into `spec` (ncomp, n0, n1, nh); the names of the launches are appended to `names`
@@ -522,10 +621,55 @@ int forward(const NGrid &n, int ncomp, const void *in, cplx *spec, hipStream_t s
     return 0;
 }
 
-}  // namespace
+// The inverse of `forward`: axis 0, then axis 1 of the half spectrum in place (`spec` is consumed), then every row of the fastest axis
+// as a full complex line; the real part times 1 / size goes to the interior cells of `out`, a full array of n.  The names of the
+// launches are appended to `names`, joined by '+'.
+int inverse(const NGrid &n, int ncomp, cplx *spec, void *out, hipStream_t st, std::string *names)
+{
+    const cplx *tw[3];
+    PDEHIP_TRY(fft_tables(st, n.n, tw));
+    const long nh = n.n[2] / 2 + 1;
+    for (int ax = 0; ax <= 1; ax++) {
+        if (n.n[ax] < 2) continue;
+        LinesArgs a;
+        a.spec = spec; a.log2n = log2_of(n.n[ax]); a.tw = tw[ax];
+        a.outer = ax == 1 ? (long)ncomp * n.n[0] : (long)ncomp;
+        a.width = ax == 1 ? nh : n.n[1] * nh;
+        const long tile = n.n[ax] * kTileMin >= kTileElems ? kTileMin : kTileElems / n.n[ax];
+        a.log2t = log2_of(tile);
+        const long items = a.outer * ((a.width + tile - 1) / tile);
+        const size_t lds = sizeof(cplx) * ((size_t)n.n[ax] * tile + n.n[ax] / 2);
+        PDEHIP_TRY(allow_lds(&inverse_lines_kernel, lds));
+        hipLaunchKernelGGL(inverse_lines_kernel, dim3(clamp_blocks(items, kFftBlocksMax)), dim3(256), lds, st, a);
+        PDEHIP_HIP(hipGetLastError());
+        *names += "inverse_lines_kernel+";
+    }
+    InvRowsArgs a;
+    a.g = make_row_grid(n); a.pc = n.pc; a.rows = n.n[0] * n.n[1]; a.log2n = log2_of(n.n[2]); a.nh = (int)nh;
+    a.batch = (int)(n.n[2] >= 512 ? 1 : 512 / n.n[2]);
+    a.inv_size = 1.0 / (double)(n.n[0] * n.n[1] * n.n[2]);
+    a.in = spec; a.out = out; a.tw = tw[2];
+    const long batches = (a.rows + a.batch - 1) / a.batch;
+    const size_t lds = sizeof(cplx) * ((size_t)a.batch * n.n[2] + n.n[2] / 2);
+    const dim3 grid(clamp_blocks(batches, kFftBlocksMax), ncomp);
+    if (n.dtype == PDEHIP_F64) {
+        PDEHIP_TRY(allow_lds(&inverse_rows_kernel<double>, lds));
+        hipLaunchKernelGGL((inverse_rows_kernel<double>), grid, dim3(256), lds, st, a);
+    } else {
+        PDEHIP_TRY(allow_lds(&inverse_rows_kernel<float>, lds));
+        hipLaunchKernelGGL((inverse_rows_kernel<float>), grid, dim3(256), lds, st, a);
+    }
+    PDEHIP_HIP(hipGetLastError());
+    *names += n.dtype == PDEHIP_F64 ? "inverse_rows_kernel<double>" : "inverse_rows_kernel<float>";
+    return 0;
+}
+
+}  // namespace fft
 }  // namespace pdehip
 
 using namespace pdehip;
+using pdehip::fft::forward;
+using pdehip::fft::inverse;
 
 extern "C" int pdehip_fft_supported(const pdehip_grid_t *g)
 {
@@ -542,6 +686,19 @@ extern "C" int pdehip_fft_forward(const pdehip_grid_t *g, int ncomp, const void 
     if ((((uintptr_t)arr_full | (uintptr_t)spectrum_dev) & 15) != 0) PDEHIP_FAIL(E_VALUE, "fft_forward: misaligned array (16 bytes for the field and the spectrum)");
     std::string names;
     PDEHIP_TRY(forward(n, ncomp, arr_full, (cplx *)spectrum_dev, as_stream(stream), &names));
+    note_kernel("%s", names.c_str());
+    return 0;
+}
+
+extern "C" int pdehip_fft_inverse(const pdehip_grid_t *g, int ncomp, void *spectrum_dev, void *out_full, void *stream)
+{
+    NGrid n;
+    PDEHIP_TRY(fft_check(g, &n));
+    if (!spectrum_dev || !out_full) PDEHIP_FAIL(E_VALUE, "fft_inverse: NULL pointer");
+    if (ncomp < 1 || ncomp > 64) PDEHIP_FAIL(E_VALUE, "fft_inverse: 1..64 components");
+    if ((((uintptr_t)spectrum_dev | (uintptr_t)out_full) & 15) != 0) PDEHIP_FAIL(E_VALUE, "fft_inverse: misaligned array (16 bytes for the spectrum and the field)");
+    std::string names;
+    PDEHIP_TRY(inverse(n, ncomp, (cplx *)spectrum_dev, out_full, as_stream(stream), &names));
     note_kernel("%s", names.c_str());
     return 0;
 }

@@ -385,6 +385,9 @@ OPTIONAL_PROTOTYPES: dict[str, list] = {
     "fft_supported": [_pg],
     "fft_forward": [_pg, _i, _vp, _vp, _vp],
     "shell_spectrum": [_pg, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp],
+    # the inverse transform, and Poisson's equation on all-periodic grids solved by it (csrc/pdehip_fft.hip, csrc/pdehip_fftsolve.hip)
+    "fft_inverse": [_pg, _i, _vp, _vp, _vp],
+    "poisson_fft": [_pg, _vp, _vp, C.POINTER(Poisson), _vp],
 }
 
 PROJECT_SUM, PROJECT_MAX, PROJECT_MIN = 0, 1, 2

@@ -9,6 +9,12 @@ the loop is allowed to see - which conditions keep the matrix symmetric - and tu
 
 ``method="mgcg"`` preconditions the same loop with one geometric multigrid V-cycle per iteration (``pdehip_poisson_set_multigrid``,
 csrc/pdehip_poisson_mg.h): the iteration count no longer grows with the extent of the grid.  ``"auto"`` and ``"cg"`` are the plain loop.
+
+``method="fft"`` is a direct solve for grids that are periodic on every axis (``pdehip_poisson_fft``, csrc/pdehip_fftsolve.hip): there the
+matrix is diagonal in Fourier space, so a forward transform, one division per mode and an inverse transform give the zero-mean solution
+to rounding - no iteration, no handle, ``maxiter`` / ``batch`` / ``mg_*`` do not apply.  Extents must be powers of two (up to 1024, 4096
+on the last axis).  ``rtol`` / ``atol`` are tested against the TRUE residual ``||A x - (f - mean f)||``, which no fp64 method brings
+below about ``2**-53 ||A|| ||x||``: a solve that misses them raises ``ConvergenceError`` instead of hiding it.
 """
 
 from __future__ import annotations
@@ -23,6 +29,8 @@ from .device import DeviceArray
 ENTRY_POINTS = ("poisson_create", "poisson_solve", "poisson_destroy")
 MG_ENTRY_POINTS = ("poisson_set_multigrid", "poisson_precondition")
 METHODS = ("auto", "cg", "mgcg")
+DIRECT_METHODS = ("fft",)
+FFT_ENTRY_POINTS = ("fft_supported", "poisson_fft")
 MG_DEFAULTS = {"mg_smooth": 2, "mg_coarse": 32, "mg_levels": None}
 MG_MAXITER = 200
 DEFAULT_RTOL = 1e-10
@@ -30,8 +38,9 @@ DEFAULT_BATCH = 32
 
 
 def check_method(method: str) -> None:
-    """``method`` of the operator: "auto", "cg" or "mgcg" (the reference: "auto" or "scipy", same message, common.py:95-97)."""
-    if method not in METHODS:
+    """``method`` of the operator: "auto", "cg", "mgcg" or the direct "fft" (the reference: "auto" or "scipy", same message,
+    common.py:95-97)."""
+    if method not in METHODS and method not in DIRECT_METHODS:
         msg = f"Method {method} is not available"
         raise ValueError(msg)
 
@@ -112,6 +121,32 @@ def is_singular(faces, ndim: int, factor_arrays=None) -> bool:
     return True
 
 
+def check_all_periodic(grid, bcs) -> None:
+    """Refuse, for the direct solve, everything but plainly periodic conditions on every axis; nothing touches the device."""
+    from .bc_expr import expression_faces
+    from .faces import convert_bcs
+
+    for axis, periodic in enumerate(grid.periodic):
+        if not periodic:
+            msg = f"poisson_solver: method=\"fft\" needs periodic conditions on every axis: the {_face_name(axis, False)} is not periodic"
+            raise NotImplementedError(msg)
+    if expression_faces(bcs):
+        msg = "poisson_solver: method=\"fft\" takes plainly periodic conditions, not expressions"
+        raise NotImplementedError(msg)
+    table = convert_bcs(bcs, part=None)
+    if getattr(table, "time_dependent", False) or getattr(table, "reads_value", False):
+        msg = "poisson_solver: method=\"fft\" takes plainly periodic conditions, not time-dependent ones"
+        raise NotImplementedError(msg)
+    for axis, n in enumerate(grid.shape):
+        for upper in (False, True):
+            face = table.c[2 * axis + int(upper)]
+            plain = (face.kind == _abi.BC_ORDER1 and not face.flags and face.const_v == 0 and face.factor1 == 1
+                     and face.index1 == (0 if upper else n - 1))
+            if not plain:
+                msg = f"poisson_solver: method=\"fft\" needs periodic conditions on every axis: the {_face_name(axis, upper)} is not plainly periodic"
+                raise NotImplementedError(msg)
+
+
 def check_conditions(bcs) -> None:
     """Refuse conditions the face table cannot show: complex factors (they couple real and imaginary part) and expressions that are
     not affine in the adjacent value (the reference refuses expression conditions in its matrix too, local.py:1086-1089)."""
@@ -181,6 +216,27 @@ class _Solver:
                 "singular": bool(io.singular), "check_residual": float(io.check_residual)}
 
 
+class _FftSolver:
+    """The direct solve of an all-periodic grid: no handle, no faces - one call of ``pdehip_poisson_fft`` per right-hand side."""
+
+    hierarchy: dict = {}
+
+    def __init__(self, backend, grid, params: dict):
+        self.backend, self.grid, self.params = backend, grid, params
+
+    def release(self) -> None:
+        pass
+
+    def solve(self, rhs: DeviceArray, out: DeviceArray, args=None) -> dict:
+        io = _abi.Poisson()
+        io.rtol, io.atol = float(self.params["rtol"]), float(self.params["atol"])
+        self.backend._lib.poisson_fft(rhs.info.ref, rhs.ptr, out.ptr, C.byref(io), self.backend.stream)
+        return {"iterations": int(io.iterations), "residual": float(io.residual), "rhs_norm": float(io.rhs_norm),
+                "converged": io.status in (_abi.POISSON_CONVERGED, _abi.POISSON_INCONSISTENT), "status": int(io.status),
+                "singular": bool(io.singular), "check_residual": float(io.check_residual),
+                "asked": max(float(io.rtol) * float(io.rhs_norm), float(io.atol))}
+
+
 def raise_for_status(info: dict, maxiter: int, method: str = "cg") -> None:
     """The status of a solve as the exception a caller of the reference would see."""
     status = info["status"]
@@ -189,6 +245,9 @@ def raise_for_status(info: dict, maxiter: int, method: str = "cg") -> None:
     if status == _abi.POISSON_MAXITER:
         from .solvers import ConvergenceError
 
+        if method in DIRECT_METHODS:
+            msg = f"Poisson problem: the direct FFT solve reached residual {info['residual']:g}, asked {info['asked']:g}"
+            raise ConvergenceError(msg)
         name = "Multigrid-preconditioned conjugate gradients (mgcg)" if method == "mgcg" else "Conjugate gradients"
         msg = f"{name} did not converge within {maxiter} iterations (residual {info['residual']:g}, right-hand side {info['rhs_norm']:g})"
         raise ConvergenceError(msg)
@@ -210,11 +269,20 @@ def make_poisson_operator(backend, grid, bcs, dtype=None, *, method: str = "auto
 
     ``method="mgcg"``: conjugate gradients preconditioned by a multigrid V-cycle, with ``mg_smooth`` Jacobi sweeps before and after
     the coarse-grid correction (default 2), ``mg_coarse`` sweeps on the last level (32) and at most ``mg_levels`` levels (None: all);
-    ``maxiter`` defaults to 200 and ``op.info`` also holds ``levels`` and ``level_shapes``.  Axes of odd extent stop coarsening."""
+    ``maxiter`` defaults to 200 and ``op.info`` also holds ``levels`` and ``level_shapes``.  Axes of odd extent stop coarsening.
+
+    ``method="fft"``: the direct solve of grids that are periodic on every axis with power-of-two extents; takes ``rtol`` and ``atol``
+    only.  ``op.info["iterations"]`` is 0 and ``op.info["residual"]`` is the true residual norm ``||A x - (f - mean f)||``."""
     from .bc_expr import convert_bcs_with_expressions, expression_faces
     from .faces import convert_bcs, real_dtype_of
 
     check_method(method)
+    direct = method in DIRECT_METHODS
+    if direct:
+        given = sorted(name for name, value in (("maxiter", maxiter), ("batch", batch)) if value is not None)
+        if given:
+            msg = f"poisson_solver: argument(s) {given} need an iterative method (method is {method!r})"
+            raise TypeError(msg)
     mg = mg_options(method, kwargs) or None      # the options of the cycle, None for the plain loop
     if kwargs:
         msg = f"poisson_solver: unknown argument(s) {sorted(kwargs)}"
@@ -227,9 +295,17 @@ def make_poisson_operator(backend, grid, bcs, dtype=None, *, method: str = "auto
     if params["maxiter"] < 1 or params["batch"] < 1:
         msg = "poisson_solver: maxiter and batch must be positive"
         raise ValueError(msg)
-    backend.grid_info(grid, np.float64)       # Cartesian grids only (raises NotImplementedError otherwise)
+    if direct:
+        check_all_periodic(grid, bcs)
+    ginfo64 = backend.grid_info(grid, np.float64)       # Cartesian grids only (raises NotImplementedError otherwise)
     lib = backend._lib
-    if not lib.has(*ENTRY_POINTS):
+    if direct:
+        if not lib.has(*FFT_ENTRY_POINTS):
+            missing = sorted("pdehip_" + name for name in FFT_ENTRY_POINTS if name in lib.missing)
+            msg = f"hip backend: the loaded library does not export {', '.join(missing)}: no `poisson_solver` with method=\"fft\" with it"
+            raise NotImplementedError(msg)
+        lib.fft_supported(ginfo64.ref)       # the dry run: NotImplementedError with the library's message
+    elif not lib.has(*ENTRY_POINTS):
         missing = sorted("pdehip_" + name for name in ENTRY_POINTS if name in lib.missing)
         msg = f"hip backend: the loaded library does not export {', '.join(missing)}: no `poisson_solver` with it"
         raise NotImplementedError(msg)
@@ -247,7 +323,7 @@ def make_poisson_operator(backend, grid, bcs, dtype=None, *, method: str = "auto
 
     def solver_for(part) -> _Solver:
         if part not in solvers:
-            solvers[part] = _Solver(backend, grid, table_for(part), params, mg)
+            solvers[part] = _FftSolver(backend, grid, params) if direct else _Solver(backend, grid, table_for(part), params, mg)
         return solvers[part]
 
     if dtype is None or np.dtype(dtype).kind != "c":
@@ -330,7 +406,8 @@ make_poisson_solver._hip_needs_bcs = True  # type: ignore[attr-defined]
 # ---------------------------------------------------------------------------------------------
 def solve_poisson_equation(rhs, bc, *, label: str = "Solution to Poisson's equation", backend="hip", **kwargs):
     """Solve ``laplace(u) = rhs`` with the conditions ``bc`` (pde/pdes/laplace.py:28-97; ``kwargs``: ``method``, ``rtol``, ``atol``,
-    ``maxiter``, ``batch`` and, with ``method="mgcg"``, ``mg_smooth``, ``mg_coarse``, ``mg_levels``).  With periodic or Neumann conditions only, the right-hand side has to be compatible with them (its
+    ``maxiter``, ``batch`` and, with ``method="mgcg"``, ``mg_smooth``, ``mg_coarse``, ``mg_levels``; ``method="fft"``: the direct solve
+    of all-periodic grids, ``rtol`` and ``atol`` only).  With periodic or Neumann conditions only, the right-hand side has to be compatible with them (its
     integral equals the prescribed flux): otherwise a ``RuntimeError`` with the reference's hint is raised."""
     from .backend import get_backend
     from .fields import ScalarField
