@@ -13,6 +13,7 @@
 
 #include "../../include/pdehip.h"
 #include "pdehip_device.h"
+#include "pdehip_faces.h"
 #include "pdehip_slab_loops.h"
 
 namespace pdehip {
@@ -122,12 +123,7 @@ inline OutStr out_strides(const NGrid &n, int layout)
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
 // kernel launchers implemented in pdehip_kernels.hip
-// input-side BCs the stencil kernel evaluates on the fly (scalar first-order conditions)
-struct InputBCs {
-    int on[3][2];      // [normalised axis][lower, upper]
-    long idx[3][2];
-    double c[3][2], f[3][2];
-};
+// InputBCs, the input-side BCs the stencil kernel evaluates on the fly, and the conversion of face tables: pdehip_faces.h
 // periodic (1) / local (0) / not covered (-1) classification of the two faces of one axis
 inline int classify_axis(const InputBCs &fg, int ax, long n)
 {

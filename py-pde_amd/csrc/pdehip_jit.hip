@@ -68,10 +68,29 @@ struct Variant {
 struct Jit {
     std::string body;                       // statements of pde_epilogue
     std::string body2;                      // statements of pde_epilogue2 (level 2 of a fused two-pass expression)
-    std::map<std::string, Variant> cache;   // key: "T,VEC,RY,CZ,HASX,IBC" or "generic,T"
+    std::map<std::string, Variant> cache;   // key(VariantSpec) in the arithmetic mode of the build (mode_key)
 };
 std::map<std::string, Variant> g_shared;   // epilogue source(s) + variant key -> loaded kernel, for the life of the process
 std::mutex g_shared_mutex;
+// tile kernel over two passes (run_tiled): one combined handle per pair of epilogues, for the life of the process
+std::map<std::string, Jit *> g_pairs;
+std::mutex g_pairs_mutex;
+
+// replay of a captured block of Euler steps (replay_blocks): a ring of instantiated graphs and the one stream they are captured
+// from and launched into.  `mutex` is held from the lookup to the last launch and event record of a call.
+struct LoopGraph {
+    std::vector<char> key;
+    hipGraphExec_t exec = nullptr;
+};
+constexpr int kLoopGraphs = 8;
+struct ReplayState {
+    std::mutex mutex;
+    LoopGraph graphs[kLoopGraphs];
+    unsigned next = 0;
+    hipStream_t cap = nullptr;
+    hipEvent_t ev = nullptr;
+};
+ReplayState g_replay;
 
 // the generated code reads PdeDer (`d.d1[..]`, `d.d2[..]`, `d.gr[..]`): only the one-level kernels supply it
 bool uses_axis_derivatives(const Jit *j)
@@ -163,12 +182,52 @@ extern "C" __global__ void __launch_bounds__(1024) pde_kernel(pdehip::Tile2Args 
 // cache key of a variant in the current arithmetic mode (pdehip_set_fastmath)
 std::string mode_key(const std::string &key) { return (fastmath_on() && !key.empty()) ? key + "#fast" : key; }
 
-int compile_variant(Jit *j, const std::string &key_in, bool generic, const char *tname, int vec, int ry, int cz, bool hasx, bool ibc, Variant *out,
-                    int two_level = 0,    // 0: one-level kernel, E2_CUSTOM / E2_CUSTOM2: two-level kernel
-                    bool stage = false,   // one-level kernel followed by the Runge-Kutta stage epilogue (LapArgs::st_*)
-                    int wy = 1,           // waves per workgroup (stacked along the rows), one-level kernel
-                    bool tails = true)    // rows that end inside a vector / leave idle chunks in a tile (pdehip_march.inc)
+// What to build around the epilogue(s) of a handle.  Each family reads its own fields; the rest keep their defaults.
+enum class Family { generic, march, two_level, tile };
+struct VariantSpec {
+    Family family = Family::generic;
+    bool f64 = true;
+    // march: the one-level kernel (the fields of jitplan::Choice).  two_level reads `ry` as well
+    int ry = 1, cz = 1, wy = 1;   // rows / chunks per wave tile, waves per workgroup (stacked along the rows)
+    bool hasx = false;            // 3-D
+    bool ibc = false;             // faces on the fly
+    bool stage = false;           // followed by the Runge-Kutta stage epilogue (LapArgs::st_*)
+    bool tails = true;            // rows that end inside a vector / leave idle chunks in a tile (pdehip_march.inc)
+    // two_level (pdehip_march2.inc)
+    bool has_y = false;           // 3-D
+    bool second_body = false;     // level 2 applies pde_epilogue2 (E2_CUSTOM2: both passes of a two-pass expression), else pde_epilogue again
+    // tile (pdehip_tile2d.inc)
+    int tile_mode = 0;            // 2: one field, 3: two coupled fields, 4: two-pass chain of one field
+    int tile_cols = 0;            // tile columns
+};
+const char *type_name(const VariantSpec &s) { return s.f64 ? "double" : "float"; }
+
+// key of a variant in the per-handle cache
+std::string key(const VariantSpec &s)
 {
+    const std::string T = type_name(s);
+    switch (s.family) {
+    case Family::generic: return "generic," + T;
+    case Family::march:
+        return T + "," + std::to_string(s.ry) + "," + std::to_string(s.cz) + "," + (s.hasx ? "x" : "-") + (s.ibc ? "b" : "-") + (s.stage ? "s" : "-") +
+               std::to_string(s.wy) + (s.tails ? "t" : "-");
+    case Family::two_level: return (s.second_body ? "fused2," : "two,") + T + "," + std::to_string(s.ry) + (s.has_y ? ",y" : ",-");
+    case Family::tile: return (s.tile_mode == 3 ? "tile2," : (s.tile_mode == 4 ? "tile4," : "tile,")) + T + "," + std::to_string(s.tile_cols);
+    }
+    return std::string();
+}
+
+// key_in empty / out == NULL: compile only (no device needed), nothing cached
+int compile_variant(Jit *j, const VariantSpec &s, const std::string &key_in, Variant *out)
+{
+    // the spec on the wire: the -D options of the wrappers above (PDE_RY carries the tile mode, PDE_CZ the tile columns, PDE_HASX the
+    // HAS_Y of the two-level kernel)
+    const bool generic = s.family == Family::generic, tile = s.family == Family::tile, two = s.family == Family::two_level;
+    const char *tname = type_name(s);
+    const int vec = generic ? 1 : (s.f64 ? 2 : 4);
+    const int ry = tile ? s.tile_mode : s.ry, cz = tile ? s.tile_cols : (two ? 1 : s.cz), wy = s.family == Family::march ? s.wy : 1;
+    const bool hasx = two ? s.has_y : s.hasx, ibc = (two || tile) ? true : s.ibc, stage = s.stage, tails = s.tails;
+    const int two_level = tile ? kTileVariant : (two ? (s.second_body ? E2_CUSTOM2 : E2_CUSTOM) : 0);
     PDEHIP_TRY(load_rtc());
     const std::string key = mode_key(key_in);   // (the exact and the contracted build of a variant are different kernels)
     // kernels already built in this process for the same epilogue(s) and variant: every eq.solve creates new handles for the
@@ -235,6 +294,17 @@ int compile_variant(Jit *j, const std::string &key_in, bool generic, const char 
     return 0;
 }
 
+// the loaded kernel of a variant: from the handle's cache, else built (or taken from g_shared).  v == NULL: compile, do not load
+int variant_for(Jit *j, const VariantSpec &s, Variant *v)
+{
+    const std::string k = v ? key(s) : std::string();
+    if (v) {
+        auto it = j->cache.find(mode_key(k));
+        if (it != j->cache.end()) { *v = it->second; return 0; }
+    }
+    return compile_variant(j, s, k, v);
+}
+
 }  // namespace
 
 extern "C" {
@@ -255,15 +325,21 @@ int pdehip_jit_check(void *handle, int dtype, int ndim)
     if (!handle) PDEHIP_FAIL(E_VALUE, "jit_check: NULL handle");
     if (dtype != PDEHIP_F64 && dtype != PDEHIP_F32) PDEHIP_FAIL(E_NOTIMPL, "unsupported dtype code %d", dtype);
     Jit *j = static_cast<Jit *>(handle);
-    const char *tname = dtype == PDEHIP_F64 ? "double" : "float";
-    const int vec = dtype == PDEHIP_F64 ? 2 : 4;
-    PDEHIP_TRY(compile_variant(j, "", true, tname, 1, 1, 1, false, false, nullptr));
-    if (ndim >= 2) PDEHIP_TRY(compile_variant(j, "", false, tname, vec, 2, 2, ndim == 3, true, nullptr));
-    if (ndim >= 2) PDEHIP_TRY(compile_variant(j, "", false, tname, vec, 1, 4, ndim == 3, true, nullptr, 0, true));   // stage sweeps: 1-row tiles
-    if (ndim >= 2) PDEHIP_TRY(compile_variant(j, "", false, tname, vec, ndim == 3 ? 2 : 1, 1, ndim == 3, true, nullptr,
-                                              j->body2.empty() ? E2_CUSTOM : E2_CUSTOM2));
-    if (ndim == 2) PDEHIP_TRY(compile_variant(j, "", false, tname, vec, j->body2.empty() ? 2 : 3, 64, false, true, nullptr, kTileVariant));
-    return 0;
+    VariantSpec s;
+    s.f64 = dtype == PDEHIP_F64;
+    PDEHIP_TRY(variant_for(j, s, nullptr));
+    if (ndim < 2) return 0;
+    s.family = Family::march; s.ry = 2; s.cz = 2; s.hasx = ndim == 3; s.ibc = true;
+    PDEHIP_TRY(variant_for(j, s, nullptr));
+    s.ry = 1; s.cz = 4; s.stage = true;   // stage sweeps: 1-row tiles
+    PDEHIP_TRY(variant_for(j, s, nullptr));
+    VariantSpec two;
+    two.family = Family::two_level; two.f64 = s.f64; two.ry = ndim == 3 ? 2 : 1; two.has_y = ndim == 3; two.second_body = !j->body2.empty();
+    PDEHIP_TRY(variant_for(j, two, nullptr));
+    if (ndim != 2) return 0;
+    VariantSpec tile;
+    tile.family = Family::tile; tile.f64 = s.f64; tile.tile_mode = j->body2.empty() ? 2 : 3; tile.tile_cols = 64;
+    return variant_for(j, tile, nullptr);
 }
 
 // a fused two-pass expression: level 1 = body1 applied to the state, level 2 = body2 applied to the result of level 1
@@ -296,6 +372,12 @@ namespace {
 const jitplan::Knobs &jit_knobs()
 {
     static const jitplan::Knobs k = jitplan::knobs_from_env();
+    return k;
+}
+// PDEHIP_TILE2D / PDEHIP_TILE2D_CELLS / PDEHIP_JIT_GRAPH (the route of pdehip_jit_euler_run), read once per process
+const jitplan::LoopKnobs &loop_knobs()
+{
+    static const jitplan::LoopKnobs k = jitplan::loop_knobs_from_env();
     return k;
 }
 
@@ -374,23 +456,9 @@ int jit_apply_impl(void *handle, const pdehip_grid_t *g, void *in_full, const vo
     int n_fused = 0;
     if (in_faces) {
         pdehip_bc_face_t rest[2 * PDEHIP_MAX_DIM];
-        int n_rest = 0;
-        for (int ar = 0; ar < PDEHIP_MAX_DIM; ar++)
-            for (int side = 0; side < 2; side++) {
-                pdehip_bc_face_t &r = rest[2 * ar + side];
-                if (ar >= n.ndim) { memset(&r, 0, sizeof(r)); continue; }
-                r = in_faces[2 * ar + side];
-                if (r.kind == PDEHIP_BC_SKIP) continue;
-                const int ax = 3 - n.ndim + ar;
-                if ((fast || n.ndim == 1) && r.kind == PDEHIP_BC_ORDER1 && r.flags == 0 && r.index1 >= 0 && r.index1 < n.n[ax]) {   // 1-D: the generic kernel does it too
-                    fg.on[ax][side] = 1; fg.idx[ax][side] = r.index1; fg.c[ax][side] = r.const_v; fg.f[ax][side] = r.factor1;
-                    r.kind = PDEHIP_BC_SKIP;
-                    n_fused++;
-                } else {
-                    n_rest++;
-                }
-            }
-        if (n_rest) PDEHIP_TRY(launch_ghosts(n, 1, rest, in_full, as_stream(stream)));
+        const FaceSplit split = split_faces(n.ndim, n.n, in_faces, fast || n.ndim == 1, 7, &fg, rest);   // 1-D: the generic kernel does it too
+        if (split.rest) PDEHIP_TRY(launch_ghosts(n, 1, rest, in_full, as_stream(stream)));
+        n_fused = split.fused;
     }
     for (int ax = 0; ax < 3; ax++)
         for (int side = 0; side < 2; side++) {
@@ -399,31 +467,26 @@ int jit_apply_impl(void *handle, const pdehip_grid_t *g, void *in_full, const vo
         }
     a.any_ibc = n_fused > 0;
 
-    Variant v;
-    const char *tname = f64 ? "double" : "float";
     jitplan::Query q;
     q.elem = f64 ? 8 : 4; q.ndim = n.ndim; q.n0 = n.n[0]; q.n1 = n.n[1]; q.n2 = n.n[2];
     q.aligned = aligned; q.stage = stage != nullptr; q.kind = stage ? stage->kind : 0;
     q.nk = !stage ? 0 : (stage->k[1] ? 2 : (stage->k[0] ? 1 : 0));
     q.fused = n_fused > 0;
     const jitplan::Choice c = jitplan::plan(q, jit_knobs());
+    VariantSpec spec;
+    spec.f64 = f64;
     if (!c.generic) {
-        const std::string key = std::string(tname) + "," + std::to_string(c.ry) + "," + std::to_string(c.cz) + "," + (c.hasx ? "x" : "-") + (c.ibc ? "b" : "-") +
-                                (c.stage ? "s" : "-") + std::to_string(c.wy) + (c.tails ? "t" : "-");
-        auto it = j->cache.find(mode_key(key));
-        if (it != j->cache.end()) v = it->second;
-        else PDEHIP_TRY(compile_variant(j, key, false, tname, c.vec, c.ry, c.cz, c.hasx, c.ibc, &v, 0, c.stage, c.wy, c.tails));
+        spec.family = Family::march;
+        spec.ry = c.ry; spec.cz = c.cz; spec.wy = c.wy;
+        spec.hasx = c.hasx; spec.ibc = c.ibc; spec.stage = c.stage; spec.tails = c.tails;
         a.ntz = c.ntz;
         a.nty = c.nty;
         a.lx = (int)c.lx;
         a.nxc = c.nxc;
         a.nblocks = c.nblocks;
-    } else {
-        const std::string key = std::string("generic,") + tname;
-        auto it = j->cache.find(mode_key(key));
-        if (it != j->cache.end()) v = it->second;
-        else PDEHIP_TRY(compile_variant(j, key, true, tname, 1, 1, 1, false, false, &v));
     }
+    Variant v;
+    PDEHIP_TRY(variant_for(j, spec, &v));
     const unsigned blocks = (unsigned)c.nblocks, threads = c.threads;
     void *args[] = {&a};
     PDEHIP_HIP(hipModuleLaunchKernel(v.fn, blocks, 1, 1, threads, 1, 1, 0, as_stream(stream), args, nullptr));
@@ -473,96 +536,58 @@ int pdehip_jit_apply_stage(void *handle, const pdehip_grid_t *g, void *in_full, 
     return jit_apply_impl(handle, g, in_full, extra3_host, k_out_full, params_host, nparams, in_faces, stream, &sf, done);
 }
 
-// TWO applications of the epilogue in one sweep: out = f(f(in)) with f(u) = pde_epilogue(u, laplace(u), gradient_squared(u);
-// params) and the BCs `faces` applied to u before each application — two explicit Euler steps of a one-pass expression PDE
-// whose epilogue is the Euler update `u + dt * F`.  The intermediate level lives in registers (pdehip_march2.inc).
-// *done = 0 and nothing launched when grid / faces are not covered (same rules as pdehip_diffusion_euler2) — the caller
-// then applies pdehip_jit_apply twice.
-int pdehip_jit_euler2(void *handle, const pdehip_grid_t *g, const void *in_full, void *out_full, const double *params_host,
-                      int nparams, const pdehip_bc_face_t *faces, int *done, void *stream)
+// One sweep of the two-level kernel (pdehip_march2.inc) around the epilogue(s) of a handle; the intermediate level lives in registers.
+// faces_tmp == NULL: level 2 applies the same epilogue with the same faces (pdehip_jit_euler2), else pde_epilogue2 with `faces_tmp`
+// (pdehip_jit_fused2).  *done = 0 and nothing launched when grid / faces are not covered (same rules as pdehip_diffusion_euler2).
+static int jit_two_level(bool fused, void *handle, const pdehip_grid_t *g, const void *in_full, void *out_full, const double *params_host,
+                         int nparams, const pdehip_bc_face_t *faces_u, const pdehip_bc_face_t *faces_tmp, int *done, void *stream)
 {
-    if (!handle || !in_full || !out_full || !faces || !done) PDEHIP_FAIL(E_VALUE, "jit_euler2: NULL pointer");
-    if (nparams < 0 || nparams > 12) PDEHIP_FAIL(E_VALUE, "jit_euler2: at most 12 scalar parameters");
+    const char *who = fused ? "jit_fused2" : "jit_euler2";
+    if (!handle || !in_full || !out_full || !faces_u || (fused && !faces_tmp) || !done) PDEHIP_FAIL(E_VALUE, "%s: NULL pointer", who);
+    if (nparams < 0 || nparams > 12) PDEHIP_FAIL(E_VALUE, "%s: at most 12 scalar parameters", who);
     *done = 0;
     Jit *j = static_cast<Jit *>(handle);
+    if (fused && j->body2.empty()) PDEHIP_FAIL(E_VALUE, "jit_fused2: handle was not created with pdehip_jit_create2");
     if (uses_axis_derivatives(j)) return 0;   // the two-level kernel evaluates laplace / gradient_squared only
     NGrid n;
     PDEHIP_TRY(norm_grid(g, &n));
     if (n.ndim < 2) return 0;
-    InputBCs fg;
-    memset(&fg, 0, sizeof(fg));
-    for (int a = 0; a < n.ndim; a++)
-        for (int side = 0; side < 2; side++) {
-            const int ax = 3 - n.ndim + a;
-            const pdehip_bc_face_t &r = faces[2 * a + side];
-            if (r.kind != PDEHIP_BC_ORDER1 || r.flags != 0 || r.index1 < 0 || r.index1 >= n.n[ax]) return 0;
-            fg.on[ax][side] = 1; fg.idx[ax][side] = r.index1; fg.c[ax][side] = r.const_v; fg.f[ax][side] = r.factor1;
-        }
+    InputBCs fg[2];
+    if (!faces_to_input_bcs(n.ndim, n.n, faces_u, &fg[0]) || (fused && !faces_to_input_bcs(n.ndim, n.n, faces_tmp, &fg[1]))) return 0;
     Euler2Plan plan;
     bool ok = false;
-    PDEHIP_TRY(launch_euler2(n, in_full, out_full, 0.0, 0.0, fg, false, as_stream(stream), &ok, false, 0, E2_CUSTOM, nullptr, 0.0, &plan));
+    PDEHIP_TRY(launch_euler2(n, in_full, out_full, 0.0, 0.0, fg[0], false, as_stream(stream), &ok, false, 0, fused ? E2_CUSTOM2 : E2_CUSTOM,
+                             fused ? &fg[1] : nullptr, 0.0, &plan));
     if (!ok) return 0;
     for (int q = 0; q < nparams; q++) plan.a.par[q] = params_host[q];
-    const bool f64 = n.dtype == PDEHIP_F64;
-    const char *tname = f64 ? "double" : "float";
-    const std::string key = std::string("two,") + tname + "," + std::to_string(plan.ry) + (plan.has_y ? ",y" : ",-");
+    VariantSpec spec;
+    spec.family = Family::two_level; spec.f64 = n.dtype == PDEHIP_F64; spec.ry = plan.ry; spec.has_y = plan.has_y; spec.second_body = fused;
     Variant v;
-    auto it = j->cache.find(mode_key(key));
-    if (it != j->cache.end()) v = it->second;
-    else PDEHIP_TRY(compile_variant(j, key, false, tname, f64 ? 2 : 4, plan.ry, 1, plan.has_y, true, &v, E2_CUSTOM));
+    PDEHIP_TRY(variant_for(j, spec, &v));
     void *kargs[] = {&plan.a};
     PDEHIP_HIP(hipModuleLaunchKernel(v.fn, plan.grid, 1, 1, plan.block, 1, 1, 0, as_stream(stream), kargs, nullptr));
-    note_kernel("pde_kernel<two,%s,%d,RY=%d,%s> (two applications of the epilogue per sweep; run-time built)", tname, f64 ? 2 : 4, plan.ry, plan.has_y ? "3-D" : "2-D");
+    note_kernel("pde_kernel<%s,%s,%d,RY=%d,%s> (%s; run-time built)", fused ? "fused2" : "two", type_name(spec), spec.f64 ? 2 : 4, plan.ry,
+                plan.has_y ? "3-D" : "2-D", fused ? "both passes of the expression in one sweep" : "two applications of the epilogue per sweep");
     *done = 1;
     return 0;
 }
 
-// ONE sweep for a two-pass expression  tmp = f1(u, lap u, |grad u|^2),  out = f2(tmp, lap tmp, |grad tmp|^2, e0 = u):
-// tmp lives in registers only (two-level kernel, pdehip_march2.inc).  `faces_u` are the BCs of u, `faces_tmp` those of
-// tmp (both periodic on the same axes).  *done = 0 when grid / faces are not covered: the caller runs the two passes.
+// TWO applications of the epilogue in one sweep: out = f(f(in)) with f(u) = pde_epilogue(u, laplace(u), gradient_squared(u);
+// params) and the BCs `faces` applied to u before each application - two explicit Euler steps of a one-pass expression PDE
+// whose epilogue is the Euler update `u + dt * F`.  *done = 0: the caller applies pdehip_jit_apply twice.
+int pdehip_jit_euler2(void *handle, const pdehip_grid_t *g, const void *in_full, void *out_full, const double *params_host,
+                      int nparams, const pdehip_bc_face_t *faces, int *done, void *stream)
+{
+    return jit_two_level(false, handle, g, in_full, out_full, params_host, nparams, faces, nullptr, done, stream);
+}
+
+// ONE sweep for a two-pass expression  tmp = f1(u, lap u, |grad u|^2),  out = f2(tmp, lap tmp, |grad tmp|^2, e0 = u).
+// `faces_u` are the BCs of u, `faces_tmp` those of tmp (both periodic on the same axes).  *done = 0: the caller runs the two passes.
 int pdehip_jit_fused2(void *handle, const pdehip_grid_t *g, const void *in_full, void *out_full, const double *params_host,
                       int nparams, const pdehip_bc_face_t *faces_u, const pdehip_bc_face_t *faces_tmp, int *done, void *stream)
 {
-    if (!handle || !in_full || !out_full || !faces_u || !faces_tmp || !done) PDEHIP_FAIL(E_VALUE, "jit_fused2: NULL pointer");
-    if (nparams < 0 || nparams > 12) PDEHIP_FAIL(E_VALUE, "jit_fused2: at most 12 scalar parameters");
-    *done = 0;
-    Jit *j = static_cast<Jit *>(handle);
-    if (j->body2.empty()) PDEHIP_FAIL(E_VALUE, "jit_fused2: handle was not created with pdehip_jit_create2");
-    if (uses_axis_derivatives(j)) return 0;
-    NGrid n;
-    PDEHIP_TRY(norm_grid(g, &n));
-    if (n.ndim < 2) return 0;
-    InputBCs fg[2];
-    const pdehip_bc_face_t *fsrc[2] = {faces_u, faces_tmp};
-    for (int l = 0; l < 2; l++) {
-        memset(&fg[l], 0, sizeof(fg[l]));
-        for (int a = 0; a < n.ndim; a++)
-            for (int side = 0; side < 2; side++) {
-                const int ax = 3 - n.ndim + a;
-                const pdehip_bc_face_t &r = fsrc[l][2 * a + side];
-                if (r.kind != PDEHIP_BC_ORDER1 || r.flags != 0 || r.index1 < 0 || r.index1 >= n.n[ax]) return 0;
-                fg[l].on[ax][side] = 1; fg[l].idx[ax][side] = r.index1; fg[l].c[ax][side] = r.const_v; fg[l].f[ax][side] = r.factor1;
-            }
-    }
-    Euler2Plan plan;
-    bool ok = false;
-    PDEHIP_TRY(launch_euler2(n, in_full, out_full, 0.0, 0.0, fg[0], false, as_stream(stream), &ok, false, 0, E2_CUSTOM2, &fg[1], 0.0, &plan));
-    if (!ok) return 0;
-    for (int q = 0; q < nparams; q++) plan.a.par[q] = params_host[q];
-    const bool f64 = n.dtype == PDEHIP_F64;
-    const char *tname = f64 ? "double" : "float";
-    const std::string key = std::string("fused2,") + tname + "," + std::to_string(plan.ry) + (plan.has_y ? ",y" : ",-");
-    Variant v;
-    auto it = j->cache.find(mode_key(key));
-    if (it != j->cache.end()) v = it->second;
-    else PDEHIP_TRY(compile_variant(j, key, false, tname, f64 ? 2 : 4, plan.ry, 1, plan.has_y, true, &v, E2_CUSTOM2));
-    void *kargs[] = {&plan.a};
-    PDEHIP_HIP(hipModuleLaunchKernel(v.fn, plan.grid, 1, 1, plan.block, 1, 1, 0, as_stream(stream), kargs, nullptr));
-    note_kernel("pde_kernel<fused2,%s,%d,RY=%d,%s> (both passes of the expression in one sweep; run-time built)", tname, f64 ? 2 : 4, plan.ry, plan.has_y ? "3-D" : "2-D");
-    *done = 1;
-    return 0;
+    return jit_two_level(true, handle, g, in_full, out_full, params_host, nparams, faces_u, faces_tmp, done, stream);
 }
-
 
 // ---- boundary conditions given as expressions, evaluated on the device (include/pdehip.h: pdehip_bcprog_*) ------------------------
 namespace {
@@ -809,19 +834,32 @@ int bcprog_run_pair(void *handle, double t0, double t1, void *stream)
 }  // namespace pdehip
 }  // extern "C++"
 
-// ---- fixed-step Euler loop over the passes of an expression PDE (include/pdehip.h) ---------------------------------------------
+// ---- the passes of an expression PDE (include/pdehip.h: pdehip_jit_pass_t) -------------------------------------------------------------
 namespace {
-struct LoopGraph {
-    std::vector<char> key;
-    hipGraphExec_t exec = nullptr;
+// the pass table of a loop and what its array indices refer to
+struct PassTable {
+    const pdehip_grid_t *g;
+    const pdehip_jit_pass_t *passes;
+    int npasses;
+    void *const *fixed;
+    size_t comp_bytes;   // bytes of one component of a state
 };
-constexpr int kLoopGraphs = 8;
-LoopGraph g_loop_graphs[kLoopGraphs];
-unsigned g_loop_next = 0;
-hipStream_t g_loop_cap = nullptr;
-hipEvent_t g_loop_ev = nullptr;
 
-// all passes of one evaluation: `src` / `extras` index -1 - k = component k of `cur`, `out` index -1 - k = component k of `nxt`
+int check_passes(const char *who, const pdehip_jit_pass_t *passes, int npasses, int nfixed, int ncomp)
+{
+    for (int q = 0; q < npasses; q++) {
+        const pdehip_jit_pass_t &p = passes[q];
+        if (!p.handle) PDEHIP_FAIL(E_VALUE, "%s: pass %d has no handle", who, q);
+        const int32_t idx[5] = {p.src, p.extras[0], p.extras[1], p.extras[2], p.out};
+        for (int m = 0; m < 5; m++) {
+            if (idx[m] == PDEHIP_JIT_NONE && m != 0 && m != 4) continue;
+            if (idx[m] == PDEHIP_JIT_NONE || idx[m] >= nfixed || idx[m] < -ncomp)
+                PDEHIP_FAIL(E_VALUE, "%s: pass %d refers to array %d (fixed: %d, components: %d)", who, q, (int)idx[m], nfixed, ncomp);
+        }
+    }
+    return 0;
+}
+
 // decomposed grids: the ghost layers of a pass's operand travel before the pass (pdehip_exchange_t, include/pdehip.h)
 int exchange_operand(const pdehip_grid_t *g, const pdehip_jit_pass_t &p, void *src, void *stream)
 {
@@ -838,41 +876,144 @@ void *exchange_comm(const pdehip_jit_pass_t *passes, int npasses)
     return nullptr;
 }
 
-int run_passes(const pdehip_grid_t *g, const pdehip_jit_pass_t *passes, int npasses, void *const *fixed, char *cur, char *nxt,
-               size_t comp_bytes, const double *params, void *stream, int skip_last = 0)
+// array index of a pass: >= 0 selects fixed[index], -1 - k component k of `state`
+void *pass_array(const PassTable &t, int32_t idx, char *state)
 {
-    for (int q = 0; q < npasses - skip_last; q++) {
-        const pdehip_jit_pass_t &p = passes[q];
-        auto in = [&](int32_t idx) -> void * {
-            if (idx == PDEHIP_JIT_NONE) return nullptr;
-            return idx >= 0 ? fixed[idx] : (void *)(cur + (size_t)(-1 - idx) * comp_bytes);
-        };
-        void *out = p.out >= 0 ? fixed[p.out] : (void *)(nxt + (size_t)(-1 - p.out) * comp_bytes);
-        const void *ex[3] = {in(p.extras[0]), in(p.extras[1]), in(p.extras[2])};
-        PDEHIP_TRY(exchange_operand(g, p, in(p.src), stream));
-        PDEHIP_TRY(jit_apply_impl(p.handle, g, in(p.src), ex, out, params, 2, p.faces, stream, nullptr, nullptr));
-    }
+    if (idx == PDEHIP_JIT_NONE) return nullptr;
+    return idx >= 0 ? t.fixed[idx] : (void *)(state + (size_t)(-1 - idx) * t.comp_bytes);
+}
+
+// One pass: `src` / `extras` resolved against `cur`, `out` against `nxt`; exchange the operand, apply.  sf: the pass ends a Runge-Kutta
+// stage or a fixed-point iteration whose combination runs in the same sweep where the vectorised kernel covers the grid (*done, see
+// jit_apply_impl; kind 5 writes no slope array)
+int run_pass(const PassTable &t, const pdehip_jit_pass_t &p, char *cur, char *nxt, const double *params, void *stream,
+             const StageFuse *sf = nullptr, int *done = nullptr)
+{
+    void *src = pass_array(t, p.src, cur), *out = pass_array(t, p.out, nxt);
+    const void *ex[3] = {pass_array(t, p.extras[0], cur), pass_array(t, p.extras[1], cur), pass_array(t, p.extras[2], cur)};
+    PDEHIP_TRY(exchange_operand(t.g, p, src, stream));
+    if (!sf) return jit_apply_impl(p.handle, t.g, src, ex, out, params, 2, p.faces, stream, nullptr, nullptr);
+    if (sf->kind == 5) return jit_apply_impl(p.handle, t.g, src, ex, nullptr, params, 2, p.faces, stream, sf, done);
+    int nk = 0;
+    while (nk < 5 && sf->k[nk]) nk++;
+    return pdehip_jit_apply_stage(p.handle, t.g, src, ex, out, params, 2, p.faces, sf->kind, sf->y, nk, sf->k, sf->c, sf->c_new, sf->out2, sf->err, done,
+                                  stream);
+}
+
+// all passes of one evaluation (but the last `skip_last`)
+int run_passes(const PassTable &t, char *cur, char *nxt, const double *params, void *stream, int skip_last = 0)
+{
+    for (int q = 0; q < t.npasses - skip_last; q++) PDEHIP_TRY(run_pass(t, t.passes[q], cur, nxt, params, stream));
     return 0;
 }
 
-int loop_steps(const pdehip_grid_t *g, const pdehip_jit_pass_t *passes, int npasses, void *const *fixed, char *cur, char *nxt,
-               size_t comp_bytes, double dt, double t0, int64_t first, int64_t count, void *stream, void *bc_program = nullptr)
+int loop_steps(const PassTable &t, char *cur, char *nxt, double dt, double t0, int64_t first, int64_t count, void *stream, void *bc_program = nullptr)
 {
     for (int64_t s = 0; s < count; s++) {
         const double params[2] = {dt, t0 + (double)(first + s) * dt};   // _solvers.py:100: t = t_start + i * dt
         if (bc_program) PDEHIP_TRY(pdehip_bcprog_run(bc_program, params[1], cur, stream));   // the faces of THIS step's time and state
-        for (int q = 0; q < npasses; q++) {
-            const pdehip_jit_pass_t &p = passes[q];
-            auto in = [&](int32_t idx) -> void * {
-                if (idx == PDEHIP_JIT_NONE) return nullptr;
-                return idx >= 0 ? fixed[idx] : (void *)(cur + (size_t)(-1 - idx) * comp_bytes);
-            };
-            void *out = p.out >= 0 ? fixed[p.out] : (void *)(nxt + (size_t)(-1 - p.out) * comp_bytes);
-            const void *ex[3] = {in(p.extras[0]), in(p.extras[1]), in(p.extras[2])};
-            PDEHIP_TRY(exchange_operand(g, p, in(p.src), stream));
-            PDEHIP_TRY(jit_apply_impl(p.handle, g, in(p.src), ex, out, params, 2, p.faces, stream, nullptr, nullptr));
+        PDEHIP_TRY(run_passes(t, cur, nxt, params, stream));
+        char *x = cur; cur = nxt; nxt = x;
+    }
+    return 0;
+}
+
+// ---- fixed-step Euler loop: the tile kernel, the replay of a captured block, or plain launches (route: pdehip_jit_plan.h) -----------------
+// 2-D grids of a few MB: K = 8 steps per launch with the time levels in LDS (pdehip_tile2d.inc around the generated update) - such grids
+// are bound by launch / dependency latency, not by bytes.  Mode 2, one field: ONE pass of the state alone.  Mode 3, two fields
+// (reaction-diffusion systems): one pass per field, each reading its own component through the stencil and at most the OTHER component's
+// centre value (slot e0); both fields advance in lockstep inside the kernel (pde_epilogue for the first, pde_epilogue2 for the second).
+// Mode 4, a two-pass chain of ONE field: tmp = f1(state), state' = f2(tmp; e0 = state), like the Cahn-Hilliard pair.
+// *done = false: not covered, nothing was launched (the planner refuses before the first launch or never)
+int run_tiled(int mode, const NGrid &n, const pdehip_jit_pass_t *passes, char *cur, char *nxt, double dt, double t0, int64_t nsteps, void *stream,
+              void **result, bool *done)
+{
+    *done = false;
+    const bool pair = mode != 2;
+    Jit *j = static_cast<Jit *>(passes[0].handle);
+    if (pair) {
+        // the second field reads the first one as e0 and vice versa: when a pass does not use the other field its slot
+        // is simply ignored by its epilogue.  One combined handle per pair of epilogues, for the life of the process.
+        Jit *j1 = static_cast<Jit *>(passes[1].handle);
+        const std::string pk = j->body + (mode == 3 ? '\x02' : '\x03') + j1->body;
+        std::lock_guard<std::mutex> guard(g_pairs_mutex);
+        auto it = g_pairs.find(pk);
+        if (it == g_pairs.end()) {
+            Jit *jc = new Jit();
+            jc->body = j->body;
+            jc->body2 = j1->body;
+            it = g_pairs.emplace(pk, jc).first;
         }
-        char *t = cur; cur = nxt; nxt = t;
+        j = it->second;
+    }
+    InputBCs fc, fm;
+    if (!faces_to_input_bcs(2, n.n, passes[0].faces, &fc) || (pair && !faces_to_input_bcs(2, n.n, passes[1].faces, &fm))) return 0;
+    VariantSpec spec;
+    spec.family = Family::tile; spec.f64 = n.dtype == PDEHIP_F64; spec.tile_mode = mode;
+    const int kmax = tile2d_max_steps(mode);
+    for (int64_t s = 0; s < nsteps;) {
+        const int k = (int)((nsteps - s) < kmax ? (nsteps - s) : kmax);
+        Tile2Args ta;
+        unsigned nblocks = 0;
+        bool planned = false;
+        PDEHIP_TRY(plan_tile2d(n, cur, nxt, mode, 0.0, 0.0, 0.0, fc, pair ? &fm : nullptr, k, &ta, &nblocks, &spec.tile_cols, &planned));
+        if (!planned) return 0;
+        ta.par[0] = dt; ta.par[1] = t0; ta.t0 = t0; ta.step0 = (long)s;
+        Variant v;
+        PDEHIP_TRY(variant_for(j, spec, &v));
+        void *kargs[] = {&ta};
+        note_kernel("tile2d_kernel<%s,mode=%d,32x%d tile> (%d steps per launch, time levels in LDS; run-time built)", type_name(spec), mode, spec.tile_cols, k);
+        PDEHIP_HIP(hipModuleLaunchKernel(v.fn, nblocks, 1, 1, 1024, 1, 1, 0, as_stream(stream), kargs, nullptr));
+        s += k;
+        char *x = cur; cur = nxt; nxt = x;
+    }
+    *result = cur;
+    *done = true;
+    return 0;
+}
+
+// Launch-bound regime: replay a captured block of jitplan::kReplayBlock steps (cached per passes / arrays / dt) while whole blocks
+// remain; *s counts the steps done.  A capture that cannot be instantiated replays nothing: the plain loop takes the steps.
+// measured (256^2 Allen-Cahn, one pass per step): replaying the captured block 4.36 us per step, plain launches 3.68 us - the run-time
+// built kernels carry 1.3 KB of arguments per node; the graph stays an option (PDEHIP_JIT_GRAPH=1)
+int replay_blocks(const PassTable &t, int nfixed, int ncomp, char *cur, char *nxt, double dt, double t0, int64_t nsteps, void *stream, int64_t *s)
+{
+    constexpr int64_t kBlock = jitplan::kReplayBlock;   // even: the buffers are back in place after a block
+    std::vector<char> key;
+    auto put = [&](const void *ptr, size_t len) { key.insert(key.end(), (const char *)ptr, (const char *)ptr + len); };
+    put(t.g, sizeof(*t.g)); put(t.passes, sizeof(*t.passes) * t.npasses);
+    if (nfixed) put(t.fixed, sizeof(void *) * nfixed);
+    put(&cur, sizeof(cur)); put(&nxt, sizeof(nxt)); put(&ncomp, sizeof(ncomp)); put(&dt, sizeof(dt));
+    ReplayState &r = g_replay;
+    std::lock_guard<std::mutex> guard(r.mutex);
+    LoopGraph *entry = nullptr;
+    for (auto &e : r.graphs)
+        if (e.exec && e.key == key) { entry = &e; break; }
+    if (!r.cap) PDEHIP_HIP(hipStreamCreateWithFlags(&r.cap, hipStreamNonBlocking));
+    if (!r.ev) PDEHIP_HIP(hipEventCreateWithFlags(&r.ev, hipEventDisableTiming));
+    if (!entry) {
+        LoopGraph &e = r.graphs[r.next++ % kLoopGraphs];
+        if (e.exec) { (void)hipGraphExecDestroy(e.exec); e.exec = nullptr; }
+        hipGraph_t graph = nullptr;
+        PDEHIP_HIP(hipStreamBeginCapture(r.cap, hipStreamCaptureModeThreadLocal));
+        const int rc = loop_steps(t, cur, nxt, dt, t0, 0, kBlock, (void *)r.cap);
+        const hipError_t ce = hipStreamEndCapture(r.cap, &graph);
+        if (rc == 0 && ce == hipSuccess && hipGraphInstantiate(&e.exec, graph, nullptr, nullptr, 0) == hipSuccess) {
+            e.key = key;
+            entry = &e;
+        } else {
+            e.exec = nullptr;
+        }
+        if (graph) (void)hipGraphDestroy(graph);
+        if (rc) return rc;
+    }
+    if (entry) {
+        hipStream_t user = as_stream(stream);
+        PDEHIP_HIP(hipEventRecord(r.ev, user));
+        PDEHIP_HIP(hipStreamWaitEvent(r.cap, r.ev, 0));
+        for (; *s + kBlock <= nsteps; *s += kBlock) PDEHIP_HIP(hipGraphLaunch(entry->exec, r.cap));
+        PDEHIP_HIP(hipEventRecord(r.ev, r.cap));
+        PDEHIP_HIP(hipStreamWaitEvent(user, r.ev, 0));
     }
     return 0;
 }
@@ -887,153 +1028,30 @@ int pdehip_jit_euler_run(const pdehip_grid_t *g, const pdehip_jit_pass_t *passes
     if (npasses < 1 || ncomp < 1 || nsteps < 0) PDEHIP_FAIL(E_VALUE, "jit_euler_run: bad pass / component / step count");
     NGrid n;
     PDEHIP_TRY(norm_grid(g, &n));
-    const size_t comp_bytes = (size_t)n.pc * elem_size(n.dtype);
-    for (int q = 0; q < npasses; q++) {
-        const pdehip_jit_pass_t &p = passes[q];
-        if (!p.handle) PDEHIP_FAIL(E_VALUE, "jit_euler_run: pass %d has no handle", q);
-        const int32_t idx[5] = {p.src, p.extras[0], p.extras[1], p.extras[2], p.out};
-        for (int m = 0; m < 5; m++) {
-            if (idx[m] == PDEHIP_JIT_NONE && m != 0 && m != 4) continue;
-            if (idx[m] == PDEHIP_JIT_NONE || idx[m] >= nfixed || idx[m] < -ncomp)
-                PDEHIP_FAIL(E_VALUE, "jit_euler_run: pass %d refers to array %d (fixed: %d, components: %d)", q, (int)idx[m], nfixed, ncomp);
-        }
-    }
+    PDEHIP_TRY(check_passes("jit_euler_run", passes, npasses, nfixed, ncomp));
+    const PassTable t = {g, passes, npasses, fixed, (size_t)n.pc * elem_size(n.dtype)};
     char *cur = (char *)state_a, *nxt = (char *)state_b;
-    int64_t s = 0;
-    // 2-D grids of a few MB and a ONE-pass expression of the state alone: K = 8 steps per launch with the time levels in LDS
-    // (pdehip_tile2d.inc around the generated update) - such grids are bound by launch / dependency latency, not by bytes
-    {
-        static int tile_on = -1;
-        static long tile_cells = 1L << 21;
-        if (tile_on < 0) {
-            const char *e = getenv("PDEHIP_TILE2D");
-            tile_on = (e && (e[0] == '0' || !strcmp(e, "off"))) ? 0 : 1;
-            if ((e = getenv("PDEHIP_TILE2D_CELLS")) != nullptr) tile_cells = atol(e);
-        }
-        // one field: ONE pass of the state alone.  Two fields (reaction-diffusion systems): one pass per field, each reading its
-        // own component through the stencil and at most the OTHER component's centre value (slot e0): both fields advance in
-        // lockstep inside the kernel (pde_epilogue for the first, pde_epilogue2 for the second)
-        const pdehip_jit_pass_t &p = passes[0];
-        auto none = [](int32_t v) { return v == PDEHIP_JIT_NONE; };
-        auto own_pass = [&](const pdehip_jit_pass_t &q, int comp, int other) {
-            return q.src == -1 - comp && q.out == -1 - comp && (none(q.extras[0]) || q.extras[0] == -1 - other) && none(q.extras[1]) &&
-                   none(q.extras[2]) && q.faces && static_cast<Jit *>(q.handle)->body2.empty();
-        };
-        const bool one = npasses == 1 && ncomp == 1 && own_pass(p, 0, 0) && none(p.extras[0]);
-        const bool two = npasses == 2 && ncomp == 2 && own_pass(passes[0], 0, 1) && own_pass(passes[1], 1, 0);
-        // two-pass chain of ONE field: tmp = f1(state), state' = f2(tmp; e0 = state) (mode 4, like the Cahn-Hilliard pair)
-        const bool chain = npasses == 2 && ncomp == 1 && p.src == -1 && p.out >= 0 && none(p.extras[0]) && none(p.extras[1]) && none(p.extras[2]) &&
-                           p.faces && passes[1].src == p.out && passes[1].out == -1 && (none(passes[1].extras[0]) || passes[1].extras[0] == -1) &&
-                           none(passes[1].extras[1]) && none(passes[1].extras[2]) && passes[1].faces &&
-                           static_cast<Jit *>(p.handle)->body2.empty() && static_cast<Jit *>(passes[1].handle)->body2.empty();
-        if (tile_on && !bc_program && (one || two || chain) && n.ndim == 2 && n.n[1] * n.n[2] <= tile_cells && nsteps >= 2) {   // (explicit time: evaluated per level)
-            Jit *j = static_cast<Jit *>(p.handle);
-            if (two || chain) {
-                // the second field reads the first one as e0 and vice versa: when a pass does not use the other field its slot
-                // is simply ignored by its epilogue.  One combined handle per pair of epilogues, for the life of the process.
-                static std::map<std::string, Jit *> pairs;
-                static std::mutex pairs_mutex;
-                Jit *j1 = static_cast<Jit *>(passes[1].handle);
-                const std::string pk = j->body + (two ? '\x02' : '\x03') + j1->body;
-                std::lock_guard<std::mutex> guard(pairs_mutex);
-                auto it = pairs.find(pk);
-                if (it == pairs.end()) {
-                    Jit *jc = new Jit();
-                    jc->body = j->body;
-                    jc->body2 = j1->body;
-                    it = pairs.emplace(pk, jc).first;
-                }
-                j = it->second;
-            }
-            InputBCs fc, fm;
-            memset(&fc, 0, sizeof(fc));
-            memset(&fm, 0, sizeof(fm));
-            bool ok = true;
-            for (int f = 0; f < ((two || chain) ? 2 : 1) && ok; f++)
-                for (int a = 0; a < 2 && ok; a++)
-                    for (int side = 0; side < 2; side++) {
-                        const pdehip_bc_face_t &r = passes[f].faces[2 * a + side];
-                        const int ax = 1 + a;
-                        if (r.kind != PDEHIP_BC_ORDER1 || r.flags != 0 || r.index1 < 0 || r.index1 >= n.n[ax]) { ok = false; break; }
-                        InputBCs &t = f ? fm : fc;
-                        t.on[ax][side] = 1; t.idx[ax][side] = r.index1; t.c[ax][side] = r.const_v; t.f[ax][side] = r.factor1;
-                    }
-            const int mode = two ? 3 : (chain ? 4 : 2);
-            const int kmax = tile2d_max_steps(mode);
-            while (ok && s < nsteps) {
-                const int k = (int)((nsteps - s) < kmax ? (nsteps - s) : kmax);
-                Tile2Args ta;
-                unsigned nblocks = 0;
-                int tcw = 0;
-                bool done = false;
-                PDEHIP_TRY(plan_tile2d(n, cur, nxt, mode, 0.0, 0.0, 0.0, fc, (two || chain) ? &fm : nullptr, k, &ta, &nblocks, &tcw, &done));
-                if (!done) { ok = false; break; }
-                ta.par[0] = dt; ta.par[1] = t0; ta.t0 = t0; ta.step0 = (long)s;
-                const char *tname = n.dtype == PDEHIP_F64 ? "double" : "float";
-                const std::string key = std::string(two ? "tile2," : (chain ? "tile4," : "tile,")) + tname + "," + std::to_string(tcw);
-                Variant v;
-                auto it = j->cache.find(mode_key(key));
-                if (it != j->cache.end()) v = it->second;
-                else PDEHIP_TRY(compile_variant(j, key, false, tname, n.dtype == PDEHIP_F64 ? 2 : 4, mode, tcw, false, true, &v, kTileVariant));
-                void *kargs[] = {&ta};
-                note_kernel("tile2d_kernel<%s,mode=%d,32x%d tile> (%d steps per launch, time levels in LDS; run-time built)", tname, mode, tcw, k);
-                PDEHIP_HIP(hipModuleLaunchKernel(v.fn, nblocks, 1, 1, 1024, 1, 1, 0, as_stream(stream), kargs, nullptr));
-                s += k;
-                char *t = cur; cur = nxt; nxt = t;
-            }
-            if (ok) { *result = cur; return 0; }
-            // (not covered: nothing was launched - `ok` can only turn false before the first launch)
-        }
+
+    jitplan::PassDesc desc[2];   // (the tile kernel takes tables of one or two passes)
+    for (int q = 0; q < npasses && q < 2; q++) {
+        const pdehip_jit_pass_t &p = passes[q];
+        desc[q] = {p.src, {p.extras[0], p.extras[1], p.extras[2]}, p.out, p.faces != nullptr, !static_cast<Jit *>(p.handle)->body2.empty()};
+    }
+    const int mode = jitplan::tile_mode(desc, npasses, ncomp, n.ndim, n.n[1], n.n[2], nsteps, bc_program != nullptr, loop_knobs());
+    if (mode) {   // (explicit time: evaluated per level)
+        bool done = false;
+        PDEHIP_TRY(run_tiled(mode, n, passes, cur, nxt, dt, t0, nsteps, stream, result, &done));
+        if (done) return 0;
     }
     // the first two steps always run as plain launches: they build whatever kernel is not built yet (no hiprtc inside a capture)
     const int64_t head = nsteps < 2 ? nsteps : 2;
-    PDEHIP_TRY(loop_steps(g, passes, npasses, fixed, cur, nxt, comp_bytes, dt, t0, 0, head, stream, bc_program));
-    s = head;
-    if (head % 2) { char *t = cur; cur = nxt; nxt = t; }
-    constexpr int64_t kBlock = 16;   // even: the buffers are back in place after a block
-    // measured (256^2 Allen-Cahn, one pass per step): replaying the captured block 4.36 us per step, plain launches from this
-    // loop 3.68 us - the run-time built kernels carry 1.3 KB of arguments per node; the graph stays an option (PDEHIP_JIT_GRAPH=1)
-    static int graphs = -1;
-    if (graphs < 0) { const char *e = getenv("PDEHIP_JIT_GRAPH"); graphs = (e && e[0] == '1') ? 1 : 0; }
-    if (graphs && !uses_time && nsteps - s >= 4 * kBlock && !exchange_comm(passes, npasses)) {   // (no RCCL groups inside a captured graph)
-        // launch-bound regime: replay a captured block (cached per passes / arrays / dt)
-        std::vector<char> key;
-        auto put = [&](const void *ptr, size_t len) { key.insert(key.end(), (const char *)ptr, (const char *)ptr + len); };
-        put(g, sizeof(*g)); put(passes, sizeof(*passes) * npasses);
-        if (nfixed) put(fixed, sizeof(void *) * nfixed);
-        put(&cur, sizeof(cur)); put(&nxt, sizeof(nxt)); put(&ncomp, sizeof(ncomp)); put(&dt, sizeof(dt));
-        LoopGraph *entry = nullptr;
-        for (auto &e : g_loop_graphs)
-            if (e.exec && e.key == key) { entry = &e; break; }
-        if (!g_loop_cap) PDEHIP_HIP(hipStreamCreateWithFlags(&g_loop_cap, hipStreamNonBlocking));
-        if (!g_loop_ev) PDEHIP_HIP(hipEventCreateWithFlags(&g_loop_ev, hipEventDisableTiming));
-        if (!entry) {
-            LoopGraph &e = g_loop_graphs[g_loop_next++ % kLoopGraphs];
-            if (e.exec) { (void)hipGraphExecDestroy(e.exec); e.exec = nullptr; }
-            hipGraph_t graph = nullptr;
-            PDEHIP_HIP(hipStreamBeginCapture(g_loop_cap, hipStreamCaptureModeThreadLocal));
-            const int rc = loop_steps(g, passes, npasses, fixed, cur, nxt, comp_bytes, dt, t0, 0, kBlock, (void *)g_loop_cap);
-            const hipError_t ce = hipStreamEndCapture(g_loop_cap, &graph);
-            if (rc == 0 && ce == hipSuccess && hipGraphInstantiate(&e.exec, graph, nullptr, nullptr, 0) == hipSuccess) {
-                e.key = key;
-                entry = &e;
-            } else {
-                e.exec = nullptr;
-            }
-            if (graph) (void)hipGraphDestroy(graph);
-            if (rc) return rc;
-        }
-        if (entry) {
-            hipStream_t user = as_stream(stream);
-            PDEHIP_HIP(hipEventRecord(g_loop_ev, user));
-            PDEHIP_HIP(hipStreamWaitEvent(g_loop_cap, g_loop_ev, 0));
-            for (; s + kBlock <= nsteps; s += kBlock) PDEHIP_HIP(hipGraphLaunch(entry->exec, g_loop_cap));
-            PDEHIP_HIP(hipEventRecord(g_loop_ev, g_loop_cap));
-            PDEHIP_HIP(hipStreamWaitEvent(user, g_loop_ev, 0));
-        }
-    }
-    PDEHIP_TRY(loop_steps(g, passes, npasses, fixed, cur, nxt, comp_bytes, dt, t0, s, nsteps - s, stream, bc_program));
-    if ((nsteps - s) % 2) { char *t = cur; cur = nxt; nxt = t; }
+    PDEHIP_TRY(loop_steps(t, cur, nxt, dt, t0, 0, head, stream, bc_program));
+    int64_t s = head;
+    if (head % 2) { char *x = cur; cur = nxt; nxt = x; }
+    if (jitplan::replay_applies(uses_time != 0, nsteps, exchange_comm(passes, npasses) != nullptr, loop_knobs()))   // (no RCCL groups inside a captured graph)
+        PDEHIP_TRY(replay_blocks(t, nfixed, ncomp, cur, nxt, dt, t0, nsteps, stream, &s));
+    PDEHIP_TRY(loop_steps(t, cur, nxt, dt, t0, s, nsteps - s, stream, bc_program));
+    if ((nsteps - s) % 2) { char *x = cur; cur = nxt; nxt = x; }
     *result = cur;
     return 0;
 }
@@ -1041,12 +1059,8 @@ int pdehip_jit_euler_run(const pdehip_grid_t *g, const pdehip_jit_pass_t *passes
 // ---- Runge-Kutta loops over the passes of an expression PDE: the generic loops of pdehip_rk_loops.h with the passes as evaluator ----
 namespace {
 struct JitEval {
-    const pdehip_grid_t *g;
-    const pdehip_jit_pass_t *passes;
-    int npasses;
-    void *const *fixed;
+    PassTable t;
     int ncomp;
-    size_t comp_bytes;
     int stage_fuse;     // 1: try the stage epilogue of the last pass, 0: never, -1: refused once (stays off)
     void *bc_program;
     // complex states as planar (re, im) pairs of components (pde_hip/complex_expr.py): the error norm of the adaptive schemes is the
@@ -1054,93 +1068,67 @@ struct JitEval {
     // explicit error field through the pointwise kernels, then pdehip_max_abs_pairs (the same calls as the host-driven loop)
     void *efield = nullptr;
 
-    int refresh(double t, const void *in, void *st) { return bc_program ? pdehip_bcprog_run(bc_program, t, in, st) : 0; }
-    // k_out = dt * F(in; t) and - where the last pass carries it - the combination `sf` in the same sweep (*fused)
-    int slope(void *in, void *k_out, double dt, double t, const StageFuse *sf, bool *fused, void *st)
+    int refresh(double time, const void *in, void *st) { return bc_program ? pdehip_bcprog_run(bc_program, time, in, st) : 0; }
+    // a fixed-point iteration whose caller left the slope array out, and the last pass cannot carry update and norm in its sweep
+    int need_scratch(const char *why)
     {
-        if (sf && sf->kind == 5) return fixedpoint_slope(in, k_out, t, sf, fused, st);
+        set_error(std::string("jit_fixedpoint_run: this ") + why);
+        return FP_NEED_SCRATCH;
+    }
+    // k_out = dt * F(in; t) and - where the last pass carries it - the combination `sf` in the same sweep (*fused)
+    int slope(void *in, void *k_out, double dt, double time, const StageFuse *sf, bool *fused, void *st)
+    {
+        // sf->kind == 5, one fixed-point iteration (pdehip_fixedpoint.h): the passes compute F itself (dt = 1) from the iterate sf->k[1]; the
+        // last one carries the update and the convergence norm where it runs on the vectorised kernel, and only else (systems, 1-D, generic
+        // kernel) the slope goes into `k_out` for the caller's pointwise kernel - so `k_out` may be NULL
+        const bool fixedpoint = sf && sf->kind == 5;
         *fused = false;
-        const double params[2] = {dt, t};
-        PDEHIP_TRY(refresh(t, in, st));
-        const pdehip_jit_pass_t &last = passes[npasses - 1];
+        const double params[2] = {fixedpoint ? 1.0 : dt, time};
+        PDEHIP_TRY(refresh(time, in, st));
+        const pdehip_jit_pass_t &last = t.passes[t.npasses - 1];
         const bool try_stage = sf && stage_fuse > 0 && ncomp == 1 && last.out == -1;
-        PDEHIP_TRY(run_passes(g, passes, npasses, fixed, (char *)in, (char *)k_out, comp_bytes, params, st, try_stage ? 1 : 0));
+        if (fixedpoint && !try_stage && !k_out) return need_scratch("right-hand side needs the scratch array for its slope");
+        PDEHIP_TRY(run_passes(t, (char *)in, (char *)k_out, params, st, try_stage ? 1 : 0));
         if (!try_stage) return 0;
-        auto arr = [&](int32_t idx) -> void * {
-            if (idx == PDEHIP_JIT_NONE) return nullptr;
-            return idx >= 0 ? fixed[idx] : (void *)((char *)in + (size_t)(-1 - idx) * comp_bytes);
-        };
-        const void *ex[3] = {arr(last.extras[0]), arr(last.extras[1]), arr(last.extras[2])};
-        int nk = 0;
-        while (nk < 5 && sf->k[nk]) nk++;
         int done = 0;
-        PDEHIP_TRY(exchange_operand(g, last, arr(last.src), st));
-        PDEHIP_TRY(pdehip_jit_apply_stage(last.handle, g, arr(last.src), ex, k_out, params, 2, last.faces, sf->kind, sf->y, nk, sf->k, sf->c,
-                                          sf->c_new, sf->out2, sf->err, &done, st));
+        PDEHIP_TRY(run_pass(t, last, (char *)in, (char *)k_out, params, st, sf, &done));
         if (done) { *fused = true; return 0; }
         stage_fuse = -1;   // only the generic kernel covers this grid: plain pass + pointwise combination from now on
+        if (fixedpoint && !k_out) return need_scratch("grid needs the scratch array for the slope");
         pdehip_jit_pass_t again = last;
         again.exchange = nullptr;   // (its operand has just been exchanged)
-        return run_passes(g, &again, 1, fixed, (char *)in, (char *)k_out, comp_bytes, params, st);
+        return run_pass(t, again, (char *)in, (char *)k_out, params, st);
     }
     const char *sweep_name() const { return nullptr; }   // (jit_apply_impl has noted the instance)
-    // One fixed-point iteration (StageFuse kind 5, pdehip_fixedpoint.h): every pass but the last as usual, the last one with the update and
-    // the convergence norm in its sweep where it runs on the vectorised kernel; else (systems, 1-D, generic kernel) the slope into
-    // `k_out` and the caller's pointwise kernel.  sf->k[1] is the iterate the passes start from.
-    int fixedpoint_slope(void *in, void *k_out, double t, const StageFuse *sf, bool *fused, void *st)
-    {
-        *fused = false;
-        const double params[2] = {1.0, t};
-        PDEHIP_TRY(refresh(t, in, st));
-        const pdehip_jit_pass_t &last = passes[npasses - 1];
-        const bool try_stage = stage_fuse > 0 && ncomp == 1 && last.out == -1;
-        if (!try_stage && !k_out) { set_error("jit_fixedpoint_run: this right-hand side needs the scratch array for its slope"); return FP_NEED_SCRATCH; }
-        PDEHIP_TRY(run_passes(g, passes, npasses, fixed, (char *)in, (char *)k_out, comp_bytes, params, st, try_stage ? 1 : 0));
-        if (!try_stage) return 0;
-        auto arr = [&](int32_t idx) -> void * {
-            if (idx == PDEHIP_JIT_NONE) return nullptr;
-            return idx >= 0 ? fixed[idx] : (void *)((char *)in + (size_t)(-1 - idx) * comp_bytes);
-        };
-        const void *ex[3] = {arr(last.extras[0]), arr(last.extras[1]), arr(last.extras[2])};
-        int done = 0;
-        PDEHIP_TRY(exchange_operand(g, last, arr(last.src), st));
-        PDEHIP_TRY(jit_apply_impl(last.handle, g, arr(last.src), ex, nullptr, params, 2, last.faces, st, sf, &done));
-        if (done) { *fused = true; return 0; }
-        stage_fuse = -1;   // only the generic kernel covers this grid: plain pass + pointwise update from now on
-        if (!k_out) { set_error("jit_fixedpoint_run: this grid needs the scratch array for the slope"); return FP_NEED_SCRATCH; }
-        pdehip_jit_pass_t again = last;
-        again.exchange = nullptr;
-        return run_passes(g, &again, 1, fixed, (char *)in, (char *)k_out, comp_bytes, params, st);
-    }
-    int lincomb(void *out, const void *y, int n, const double *c, const void *const *k, void *st) { return pdehip_lincomb(g, ncomp, out, y, n, c, k, st); }
-    int rk4_combine(void *y, const void *k1, const void *k2, const void *k3, const void *k4, void *st) { return pdehip_rk4_combine(g, ncomp, y, k1, k2, k3, k4, st); }
+    int lincomb(void *out, const void *y, int n, const double *c, const void *const *k, void *st) { return pdehip_lincomb(t.g, ncomp, out, y, n, c, k, st); }
+    int rk4_combine(void *y, const void *k1, const void *k2, const void *k3, const void *k4, void *st) { return pdehip_rk4_combine(t.g, ncomp, y, k1, k2, k3, k4, st); }
     int rkf45_combine(const void *y, void *ynew, const void *const *k6, double *err, void *st)
     {
-        if (!efield) return pdehip_rkf45_combine(g, ncomp, y, ynew, k6, err, st);
+        if (!efield) return pdehip_rkf45_combine(t.g, ncomp, y, ynew, k6, err, st);
         const double c[4] = {25.0 / 216, 1408.0 / 2565, 2197.0 / 4104, -1.0 / 5};                        // runge_kutta.py:150
         const double r[5] = {1.0 / 360, -128.0 / 4275, -2197.0 / 75240, 1.0 / 50, 2.0 / 55};             // runge_kutta.py:147
         const void *kc[4] = {k6[0], k6[2], k6[3], k6[4]}, *kr[5] = {k6[0], k6[2], k6[3], k6[4], k6[5]};
-        PDEHIP_TRY(pdehip_lincomb(g, ncomp, ynew, y, 4, c, kc, st));
-        PDEHIP_TRY(pdehip_lincomb(g, ncomp, efield, nullptr, 5, r, kr, st));
-        return pdehip_max_abs_pairs(g, ncomp / 2, efield, err, st);
+        PDEHIP_TRY(pdehip_lincomb(t.g, ncomp, ynew, y, 4, c, kc, st));
+        PDEHIP_TRY(pdehip_lincomb(t.g, ncomp, efield, nullptr, 5, r, kr, st));
+        return pdehip_max_abs_pairs(t.g, ncomp / 2, efield, err, st);
     }
     int euler_adaptive_combine(const void *y, const void *rate, double dt, const void *half, const void *k, void *out, double *err, void *st)
     {
-        if (!efield) return pdehip_euler_adaptive_combine(g, ncomp, y, rate, dt, half, k, out, err, st);
+        if (!efield) return pdehip_euler_adaptive_combine(t.g, ncomp, y, rate, dt, half, k, out, err, st);
         const double one = 1.0, minus = -1.0;
         const void *kk[1] = {k};
-        PDEHIP_TRY(pdehip_lincomb(g, ncomp, out, half, 1, &one, kk, st));         // step_small += 0.5 * dt * rate_midpoint
+        PDEHIP_TRY(pdehip_lincomb(t.g, ncomp, out, half, 1, &one, kk, st));         // step_small += 0.5 * dt * rate_midpoint
         kk[0] = rate;
-        PDEHIP_TRY(pdehip_lincomb(g, ncomp, efield, y, 1, &dt, kk, st));          // step_large
+        PDEHIP_TRY(pdehip_lincomb(t.g, ncomp, efield, y, 1, &dt, kk, st));          // step_large
         kk[0] = out;
-        PDEHIP_TRY(pdehip_lincomb(g, ncomp, efield, efield, 1, &minus, kk, st));  // step_large - step_small
-        return pdehip_max_abs_pairs(g, ncomp / 2, efield, err, st);
+        PDEHIP_TRY(pdehip_lincomb(t.g, ncomp, efield, efield, 1, &minus, kk, st));  // step_large - step_small
+        return pdehip_max_abs_pairs(t.g, ncomp / 2, efield, err, st);
     }
     int zero(void *ptr, size_t bytes, void *st) { PDEHIP_HIP(hipMemsetAsync(ptr, 0, bytes, as_stream(st))); return 0; }
     // decomposed grids: MAX over the ranks of the communicator the passes exchange through (NaN wins); nothing on one device
     int reduce_error(double *err_dev, void *st)
     {
-        void *comm = exchange_comm(passes, npasses);
+        void *comm = exchange_comm(t.passes, t.npasses);
         return comm ? pdehip_allreduce_max(comm, err_dev, st) : 0;
     }
     int read_scalar(double *host, const double *dev, void *st)
@@ -1163,17 +1151,8 @@ static int jit_loop_run(const char *who, int scheme, const pdehip_grid_t *g, con
     if (ctl && (!ynew || !err_dev || !(ctl->tolerance > 0) || !(ctl->dt > 0))) PDEHIP_FAIL(E_VALUE, "%s: the adaptive loop needs ynew, err_dev, tolerance > 0 and dt > 0", who);
     NGrid n;
     PDEHIP_TRY(norm_grid(g, &n));
-    for (int q = 0; q < npasses; q++) {
-        const pdehip_jit_pass_t &p = passes[q];
-        if (!p.handle) PDEHIP_FAIL(E_VALUE, "jit_rk_run: pass %d has no handle", q);
-        const int32_t idx[5] = {p.src, p.extras[0], p.extras[1], p.extras[2], p.out};
-        for (int m = 0; m < 5; m++) {
-            if (idx[m] == PDEHIP_JIT_NONE && m != 0 && m != 4) continue;
-            if (idx[m] == PDEHIP_JIT_NONE || idx[m] >= nfixed || idx[m] < -ncomp)
-                PDEHIP_FAIL(E_VALUE, "jit_rk_run: pass %d refers to array %d (fixed: %d, components: %d)", q, (int)idx[m], nfixed, ncomp);
-        }
-    }
-    JitEval ev{g, passes, npasses, fixed, ncomp, (size_t)n.pc * elem_size(n.dtype), (stage_fuse & 1) ? 1 : 0, bc_program};
+    PDEHIP_TRY(check_passes(who, passes, npasses, nfixed, ncomp));
+    JitEval ev{PassTable{g, passes, npasses, fixed, (size_t)n.pc * elem_size(n.dtype)}, ncomp, (stage_fuse & 1) ? 1 : 0, bc_program};
     if (stage_fuse & 2) {   // complex pairs: one more work array, the error field (RKF45: work[7], adaptive Euler: work[3])
         if (ncomp % 2 || !ctl) PDEHIP_FAIL(E_VALUE, "%s: complex pairs need an even number of components and the adaptive loop", who);
         ev.efield = work_host[scheme == 1 ? 3 : 7];
@@ -1212,17 +1191,8 @@ int pdehip_jit_fixedpoint_run(const pdehip_grid_t *g, const pdehip_jit_pass_t *p
     if ((stage_fuse & 2) && ncomp % 2) PDEHIP_FAIL(E_VALUE, "jit_fixedpoint_run: complex pairs need an even number of components");
     NGrid n;
     PDEHIP_TRY(norm_grid(g, &n));
-    for (int q = 0; q < npasses; q++) {
-        const pdehip_jit_pass_t &p = passes[q];
-        if (!p.handle) PDEHIP_FAIL(E_VALUE, "jit_fixedpoint_run: pass %d has no handle", q);
-        const int32_t idx[5] = {p.src, p.extras[0], p.extras[1], p.extras[2], p.out};
-        for (int m = 0; m < 5; m++) {
-            if (idx[m] == PDEHIP_JIT_NONE && m != 0 && m != 4) continue;
-            if (idx[m] == PDEHIP_JIT_NONE || idx[m] >= nfixed || idx[m] < -ncomp)
-                PDEHIP_FAIL(E_VALUE, "jit_fixedpoint_run: pass %d refers to array %d (fixed: %d, components: %d)", q, (int)idx[m], nfixed, ncomp);
-        }
-    }
-    JitEval ev{g, passes, npasses, fixed, ncomp, (size_t)n.pc * elem_size(n.dtype), (stage_fuse & 1) ? 1 : 0, bc_program};
+    PDEHIP_TRY(check_passes("jit_fixedpoint_run", passes, npasses, nfixed, ncomp));
+    JitEval ev{PassTable{g, passes, npasses, fixed, (size_t)n.pc * elem_size(n.dtype)}, ncomp, (stage_fuse & 1) ? 1 : 0, bc_program};
     // `state.size` of the reference: every stored value, a complex value once (implicit.py:99-102 sums |d|^2 = re^2 + im^2)
     const double size = (double)n.n[0] * (double)n.n[1] * (double)n.n[2] * (double)((stage_fuse & 2) ? ncomp / 2 : ncomp);
     return fp::run(ev, g, ncomp, size, fp, dt, t0, nsteps, state_full, work4_host, (double *)ctl_dev, ctl_bytes, result, stream);

@@ -1,11 +1,14 @@
 // pdehip_jit_plan.h - what a run-time built one-level sweep (pdehip_jit.hip: lap_march_body<..., LAP_CUSTOM, ...> around a generated epilogue)
 // runs: the generic kernel or the instance (RY, CZ, WY, HASX, IBC, STAGE, TAILS), and the launch geometry (wave tiles per plane, planes per
-// workgroup, x-chunks, workgroups, threads).  Plain host C++17 without a HIP header: pdehip_jit.hip asks plan() and launches what it answers,
-// a CPU test (tests/test_jit_cases_cpu.py through tests/shim/jit_plan_probe.cpp) asks the same function.
+// workgroup, x-chunks, workgroups, threads); and which route the fixed-step Euler loop takes (tile_mode, replay_applies).  Plain host C++17
+// without a HIP header: pdehip_jit.hip asks plan() and launches what it answers, CPU tests (tests/test_jit_cases_cpu.py,
+// tests/test_tile2d_cases_cpu.py through tests/shim/jit_plan_probe.cpp) ask the same functions.
 #pragma once
 
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 
 namespace pdehip {
 namespace jitplan {
@@ -111,6 +114,61 @@ inline void format_name(const Choice &c, char *buf, size_t size)
     if (c.generic) { snprintf(buf, size, "pde_kernel<generic,%s> (run-time built)", T); return; }
     snprintf(buf, size, "pde_kernel<%s,%d,RY=%d,CZ=%d,WY=%d,%s,%s,%s,%s> (lx=%ld, %ld x-chunk%s; run-time built)", T, c.vec, c.ry, c.cz, c.wy,
              c.hasx ? "3-D" : "2-D", c.ibc ? "ibc" : "-", c.stage ? "stage" : "-", c.tails ? "tails" : "-", c.lx, c.nxc, c.nxc == 1 ? "" : "s");
+}
+
+// ---- the route of the fixed-step Euler loop (pdehip_jit_euler_run): the tile kernel, the replay of a captured block, or plain launches ----
+struct LoopKnobs {
+    bool tile = true;              // PDEHIP_TILE2D: "0" / "off" keeps the loop away from the tile kernel
+    long tile_cells = 1L << 21;    // PDEHIP_TILE2D_CELLS: the largest grid the tile kernel takes
+    bool graph = false;            // PDEHIP_JIT_GRAPH=1: replay a captured block of steps
+};
+inline LoopKnobs loop_knobs_from_env()
+{
+    LoopKnobs k;
+    const char *e = getenv("PDEHIP_TILE2D");
+    k.tile = !(e && (e[0] == '0' || !strcmp(e, "off")));
+    if ((e = getenv("PDEHIP_TILE2D_CELLS")) != nullptr) k.tile_cells = atol(e);
+    k.graph = (e = getenv("PDEHIP_JIT_GRAPH")) && e[0] == '1';
+    return k;
+}
+
+// what the route reads of a pass (pdehip_jit_pass_t, include/pdehip.h)
+constexpr int kNoArray = INT32_MIN;   // PDEHIP_JIT_NONE
+struct PassDesc {
+    int src, extras[3], out;   // >= 0: a fixed array, -1 - k: component k of the state, kNoArray
+    bool faces;                // the pass has a table of conditions
+    bool second_body;          // its handle carries a second epilogue (pdehip_jit_create2)
+};
+
+// The mode in which the tile kernel (pdehip_tile2d.inc) takes the loop, or 0.  p: the first min(npasses, 2) passes.
+//   2, one field: ONE pass of the state alone
+//   3, two fields: one pass per field, each reading its own component through the stencil and at most the OTHER component's centre value (slot e0)
+//   4, a two-pass chain of ONE field: tmp = f1(state), state' = f2(tmp; e0 = state)
+// n1, n2: rows and lanes of the 2-D grid.  (Whether the kernel covers the faces of the passes is plan_tile2d's decision, after this one.)
+inline int tile_mode(const PassDesc *p, int npasses, int ncomp, int ndim, long n1, long n2, long nsteps, bool bc_program, const LoopKnobs &k)
+{
+    if (!k.tile || bc_program || ndim != 2 || n1 * n2 > k.tile_cells || nsteps < 2) return 0;
+    auto none = [](int v) { return v == kNoArray; };
+    auto own_pass = [&](const PassDesc &q, int comp, int other) {
+        return q.src == -1 - comp && q.out == -1 - comp && (none(q.extras[0]) || q.extras[0] == -1 - other) && none(q.extras[1]) && none(q.extras[2]) &&
+               q.faces && !q.second_body;
+    };
+    if (npasses == 1 && ncomp == 1 && own_pass(p[0], 0, 0) && none(p[0].extras[0])) return 2;
+    if (npasses == 2 && ncomp == 2 && own_pass(p[0], 0, 1) && own_pass(p[1], 1, 0)) return 3;
+    if (npasses == 2 && ncomp == 1 && p[0].src == -1 && p[0].out >= 0 && none(p[0].extras[0]) && none(p[0].extras[1]) && none(p[0].extras[2]) && p[0].faces &&
+        p[1].src == p[0].out && p[1].out == -1 && (none(p[1].extras[0]) || p[1].extras[0] == -1) && none(p[1].extras[1]) && none(p[1].extras[2]) && p[1].faces &&
+        !p[0].second_body && !p[1].second_body)
+        return 4;
+    return 0;
+}
+
+// The replay of a captured block: the first two steps always run as plain launches (they build the kernels), then whole blocks of
+// kReplayBlock steps, worth it from four blocks on.  Explicit time changes the arguments of every step; `comm`: the passes exchange
+// ghost layers through a communicator (no RCCL groups inside a captured graph).
+constexpr long kReplayBlock = 16;
+inline bool replay_applies(bool uses_time, long nsteps, bool comm, const LoopKnobs &k)
+{
+    return k.graph && !uses_time && nsteps - 2 >= 4 * kReplayBlock && !comm;
 }
 
 }  // namespace jitplan

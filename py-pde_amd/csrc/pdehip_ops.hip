@@ -664,51 +664,15 @@ int laplace_with_input_bcs(const pdehip_grid_t *g, void *in, const void *y, void
     NGrid n;
     PDEHIP_TRY(norm_grid(g, &n));
     if (!in_faces) PDEHIP_FAIL(E_VALUE, "input faces are NULL");
-    InputBCs fg;
-    memset(&fg, 0, sizeof(fg));
-    pdehip_bc_face_t rest[2 * PDEHIP_MAX_DIM];
-    int n_rest = 0, n_fused = 0;
     static int fuse_axes = -1;   // PDEHIP_FUSE_AXES: bit per normalised axis (tuning / testing aid)
     if (fuse_axes < 0) { const char *e = getenv("PDEHIP_FUSE_AXES"); fuse_axes = e ? atoi(e) : 7; }
     // (1-D grids: the one-cell-per-thread kernel evaluates its two virtual points itself for the plain epilogues)
     const bool can_fuse = laplace_can_fuse_bcs(n, in, out, mode == LAP_EULER ? y : nullptr) || (n.ndim == 1 && mode <= LAP_CH_MU && !stage);
-    for (int a = 0; a < PDEHIP_MAX_DIM; a++)
-        for (int side = 0; side < 2; side++) {
-            pdehip_bc_face_t &r = rest[2 * a + side];
-            if (a >= n.ndim) { memset(&r, 0, sizeof(r)); continue; }
-            r = in_faces[2 * a + side];
-            if (r.kind == PDEHIP_BC_SKIP) continue;
-            const int ax = 3 - n.ndim + a;
-            if (can_fuse && ((fuse_axes >> ax) & 1) && r.kind == PDEHIP_BC_ORDER1 && r.flags == 0 && r.index1 >= 0 && r.index1 < n.n[ax]) {
-                fg.on[ax][side] = 1; fg.idx[ax][side] = r.index1; fg.c[ax][side] = r.const_v; fg.f[ax][side] = r.factor1;
-                r.kind = PDEHIP_BC_SKIP;
-                n_fused++;
-            } else {
-                n_rest++;
-            }
-        }
-    if (n_rest) PDEHIP_TRY(launch_ghosts(n, 1, rest, in, as_stream(stream)));
-    return launch_laplace(n, in, out, out_strides(n, PDEHIP_OUT_FULL), mode, s1, s2, gamma, y, as_stream(stream), n_fused ? &fg : nullptr, stage);
-}
-
-// faces (grid axes) -> on-the-fly BC table (normalised axes); false when a face is not a scalar first-order condition
-static bool faces_to_input_bcs(const NGrid &n, const pdehip_bc_face_t *faces, InputBCs *fg, int first_axis = 0, int xplain = 0)
-{
-    memset(fg, 0, sizeof(*fg));
-    if (xplain > 1) {   // one local face on the slowest axis (first / last slab of a non-periodic axis)
-        const int side = xplain == 2 ? 0 : 1, ax = 3 - n.ndim;
-        const pdehip_bc_face_t &r = faces[side];
-        if (r.kind != PDEHIP_BC_ORDER1 || r.flags != 0 || r.index1 < 0 || r.index1 >= n.n[ax]) return false;
-        fg->on[ax][side] = 1; fg->idx[ax][side] = r.index1; fg->c[ax][side] = r.const_v; fg->f[ax][side] = r.factor1;
-    }
-    for (int a = first_axis; a < n.ndim; a++)
-        for (int side = 0; side < 2; side++) {
-            const int ax = 3 - n.ndim + a;
-            const pdehip_bc_face_t &r = faces[2 * a + side];
-            if (r.kind != PDEHIP_BC_ORDER1 || r.flags != 0 || r.index1 < 0 || r.index1 >= n.n[ax]) return false;
-            fg->on[ax][side] = 1; fg->idx[ax][side] = r.index1; fg->c[ax][side] = r.const_v; fg->f[ax][side] = r.factor1;
-        }
-    return true;
+    InputBCs fg;
+    pdehip_bc_face_t rest[2 * PDEHIP_MAX_DIM];
+    const FaceSplit split = split_faces(n.ndim, n.n, in_faces, can_fuse, fuse_axes, &fg, rest);
+    if (split.rest) PDEHIP_TRY(launch_ghosts(n, 1, rest, in, as_stream(stream)));
+    return launch_laplace(n, in, out, out_strides(n, PDEHIP_OUT_FULL), mode, s1, s2, gamma, y, as_stream(stream), split.fused ? &fg : nullptr, stage);
 }
 
 int euler2_with_input_bcs(const pdehip_grid_t *g, const void *in, void *out, double s1, double s2,
@@ -720,7 +684,7 @@ int euler2_with_input_bcs(const pdehip_grid_t *g, const void *in, void *out, dou
     if (!in || !out || !faces) PDEHIP_FAIL(E_VALUE, "euler2: NULL pointer");
     if (n.ndim < 2) return 0;
     InputBCs fg;
-    if (!faces_to_input_bcs(n, faces, &fg, xplain ? 1 : 0, xplain)) return 0;
+    if (!faces_to_input_bcs(n.ndim, n.n, faces, &fg, xplain ? 1 : 0, xplain)) return 0;
     return launch_euler2(n, in, out, s1, s2, fg, xplain, as_stream(stream), done, dry_run, ends);
 }
 
@@ -734,7 +698,7 @@ int euler4_with_input_bcs(const pdehip_grid_t *g, const void *in, void *out, dou
     if (!in || !out || !faces) PDEHIP_FAIL(E_VALUE, "euler4: NULL pointer");
     if (n.ndim != 3) return 0;
     InputBCs fg;
-    if (!faces_to_input_bcs(n, faces, &fg)) return 0;
+    if (!faces_to_input_bcs(n.ndim, n.n, faces, &fg)) return 0;
     return launch_euler4(n, in, out, s1, s2, fg, const_faces, as_stream(stream), done);
 }
 
@@ -790,10 +754,10 @@ int euler_multi_2d(const pdehip_grid_t *g, const pdehip_rhs_t *rhs, const void *
     if (!in || !out || !rhs) PDEHIP_FAIL(E_VALUE, "euler_multi_2d: NULL pointer");
     if (n.ndim != 2) return 0;
     InputBCs fc, fm;
-    if (!faces_to_input_bcs(n, rhs->bc_c, &fc)) return 0;
+    if (!faces_to_input_bcs(n.ndim, n.n, rhs->bc_c, &fc)) return 0;
     if (rhs->kind == PDEHIP_RHS_DIFFUSION)
         return launch_tile2d(n, in, out, 0, rhs->param, dt, 0.0, fc, nullptr, nsteps, as_stream(stream), done);
-    if (rhs->kind != PDEHIP_RHS_CAHN_HILLIARD || !faces_to_input_bcs(n, rhs->bc_mu, &fm)) return 0;
+    if (rhs->kind != PDEHIP_RHS_CAHN_HILLIARD || !faces_to_input_bcs(n.ndim, n.n, rhs->bc_mu, &fm)) return 0;
     return launch_tile2d(n, in, out, 1, 1.0, dt, rhs->param, fc, &fm, nsteps, as_stream(stream), done);
 }
 
@@ -808,7 +772,7 @@ int cahn_hilliard_fused(const pdehip_grid_t *g, const void *in, void *out, doubl
     if (stage && euler) PDEHIP_FAIL(E_RUNTIME, "internal: a Runge-Kutta stage sweep computes the scaled slope");
     if (n.ndim < 2) return 0;
     InputBCs fc, fm;
-    if (!faces_to_input_bcs(n, faces_c, &fc, xplain ? 1 : 0, xplain) || !faces_to_input_bcs(n, faces_mu, &fm, xplain ? 1 : 0, xplain)) return 0;
+    if (!faces_to_input_bcs(n.ndim, n.n, faces_c, &fc, xplain ? 1 : 0, xplain) || !faces_to_input_bcs(n.ndim, n.n, faces_mu, &fm, xplain ? 1 : 0, xplain)) return 0;
     // level 2 is `y + s2 * (s1 * lap(mu))` resp. `s2 * (s1 * lap(mu))` with s1 = 1 like the two-kernel path (pdehip_steppers.hip)
     return launch_euler2(n, in, out, 1.0, dt, fc, xplain, as_stream(stream), done, dry_run, 0,
                          stage ? E2_CH_STAGE : (euler ? E2_CH_EULER : E2_CH_SCALED), &fm, gamma, nullptr, stage);

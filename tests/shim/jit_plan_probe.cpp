@@ -29,4 +29,30 @@ void jitplan_knobs_from_env(long *k)
     const Knobs K = knobs_from_env();
     k[0] = K.ry; k[1] = K.cz; k[2] = K.wy; k[3] = K.blocks;
 }
+
+// ---- the route of the fixed-step Euler loop ----
+// k[3] (NULL: the defaults): tile tile_cells graph
+static LoopKnobs loop_knobs(const long *k)
+{
+    LoopKnobs K;
+    if (k) { K.tile = k[0] != 0; K.tile_cells = k[1]; K.graph = k[2] != 0; }
+    return K;
+}
+
+// p[7 per pass, the first min(npasses, 2) passes]: src extras[0] extras[1] extras[2] out faces second_body
+// q[7]: npasses ncomp ndim n1 n2 nsteps bc_program; returns the mode of the tile kernel or 0
+long jitplan_tile_mode(const long *p, const long *q, const long *k)
+{
+    PassDesc d[2];
+    for (int i = 0; i < 2 && i < q[0]; i++, p += 7) d[i] = {(int)p[0], {(int)p[1], (int)p[2], (int)p[3]}, (int)p[4], p[5] != 0, p[6] != 0};
+    return tile_mode(d, (int)q[0], (int)q[1], (int)q[2], q[3], q[4], q[5], q[6] != 0, loop_knobs(k));
+}
+
+long jitplan_replay_applies(long uses_time, long nsteps, long comm, const long *k) { return replay_applies(uses_time != 0, nsteps, comm != 0, loop_knobs(k)); }
+
+void jitplan_loop_knobs_from_env(long *k)
+{
+    const LoopKnobs K = loop_knobs_from_env();
+    k[0] = K.tile; k[1] = K.tile_cells; k[2] = K.graph;
+}
 }

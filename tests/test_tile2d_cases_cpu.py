@@ -9,12 +9,23 @@ routed to its mode and every refusal must not, so that a fall-back cannot pass a
 
 from __future__ import annotations
 
+import ctypes as C
+import os
+import subprocess
+import sys
+from pathlib import Path
+
 import numpy as np
 import pytest
 import shimlib
 import tile2d_cases as T
 
+from pde_hip import _abi
 from pde_hip.rhs import _match_expression_rhs
+
+ROOT = Path(__file__).resolve().parent.parent
+HEADER = ROOT / "py-pde_amd" / "csrc" / "pdehip_jit_plan.h"
+PROBE = ROOT / "tests" / "shim" / "jit_plan_probe.cpp"
 
 
 def test_the_restated_planner_gives_the_hand_computed_rows():
@@ -209,3 +220,152 @@ def test_the_refusal_list_is_exactly_the_cases_that_miss_the_tile_kernel():
         _, eq, state, *_ = T.refusals()[2]
         assert T.tile_route(eq, state, 2) == 4
         assert T.tile_route(T.refusals()[0][1], T.state_of(2, (2, 1048576), "pl", "float64"), 3) == 2
+
+
+# ---- the route of pdehip_jit_euler_run, asked of the library's own header --------------------------------------------------------------
+# ``jitplan::tile_mode`` (csrc/pdehip_jit_plan.h) decides from the pass descriptors, the component count, the grid, the step count, "has a
+# boundary program" and the knobs; the classes of the faces are plan_tile2d's part and stay outside (`T.tile_route` = `T.loop_route` + faces).
+NONE = _abi.JIT_NONE
+
+
+@pytest.fixture(scope="module")
+def probe():
+    build = PROBE.parent / "_build"
+    build.mkdir(exist_ok=True)
+    so = build / "libjitplan_probe.so"
+    if not so.exists() or so.stat().st_mtime < max(HEADER.stat().st_mtime, PROBE.stat().st_mtime):
+        tmp = so.with_suffix(f".{os.getpid()}.tmp")
+        subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-shared", "-fPIC", str(PROBE), "-o", str(tmp)], check=True)
+        os.replace(tmp, so)
+    return C.CDLL(str(so))
+
+
+def _knobs(knobs):
+    return None if knobs is None else (C.c_long * 3)(*knobs)
+
+
+def header_mode(probe, rows, ncomp, shape, steps, *, bc_program=False, knobs=None, npasses=None):
+    """rows: (src, e0, e1, e2, out, faces, second_body) per pass; the mode as `T.loop_route` reports it (None: not the tile kernel)"""
+    flat = [int(v) for row in rows[:2] for v in row]
+    n = (1,) * (3 - len(shape)) + tuple(shape)
+    q = (C.c_long * 7)(len(rows) if npasses is None else npasses, ncomp, len(shape), n[1], n[2], steps, bc_program)
+    return probe.jitplan_tile_mode((C.c_long * max(len(flat), 1))(*flat), q, _knobs(knobs)) or None
+
+
+def rows_of(passes):
+    """what the library reads of the descriptors of the package (its handles are made by pdehip_jit_create: no second epilogue)"""
+    return [(p.src, *p.extras, p.out, bool(p.faces), False) for p in passes]
+
+
+def _header_route(probe, eq, state, steps):
+    passes, ncomp, program = T.loop_descriptors(eq, state)
+    mine = None if program else T.loop_route(passes, ncomp, state.grid.shape, steps)
+    assert header_mode(probe, rows_of(passes), ncomp, state.grid.shape, steps, bc_program=program) == mine
+    return mine
+
+
+@pytest.mark.parametrize("item", T.jit_items(), ids=T.jit_item_id)
+def test_the_header_routes_every_case_to_its_mode(probe, item):
+    (mode, _, _, _), cases = item
+    with shimlib.use_shim(fused=False):
+        for c in cases:
+            eq, state = T.jit_eq(c.mode, c.expr, c.faces), T.state_of(c.mode, c.shape, c.faces, c.dtype)
+            assert _header_route(probe, eq, state, c.steps) == T.tile_route(eq, state, c.steps) == mode, c.id
+
+
+def test_the_header_routes_the_refusals_and_the_launch_rows(probe):
+    by_faces = ("second-order-face", "array-face", "tables-of-other-periodicity", "one-cell-axis-of-two-classes")
+    with shimlib.use_shim(fused=False):
+        for rid, eq, state, _, _, steps in T.refusals():
+            mode = _header_route(probe, eq, state, steps)
+            assert T.tile_route(eq, state, steps) is None, rid
+            # refused by the faces alone: the header has chosen a mode and plan_tile2d declines it
+            assert (mode is not None) == (rid in by_faces), rid
+        first = {2: "allen_cahn", 3: "brusselator", 4: "swift_hohenberg"}
+        rows = [(mode, steps) for mode, steps, _ in T.LAUNCH_ROWS if mode >= 2]       # (modes 0 and 1 are the built-in sweeps: not this loop)
+        assert {m for m, _ in rows} == {2, 3, 4}
+        for mode, steps in rows:
+            eq, state = T.jit_eq(mode, first[mode], "lp"), T.state_of(mode, (33, 70), "lp", "float64")
+            assert _header_route(probe, eq, state, steps) == T.tile_route(eq, state, steps) == mode, (mode, steps)
+
+
+ONE = [(-1, NONE, NONE, NONE, -1, True, False)]
+TWO = [(-1, -2, NONE, NONE, -1, True, False), (-2, -1, NONE, NONE, -2, True, False)]
+CHAIN = [(-1, NONE, NONE, NONE, 0, True, False), (0, -1, NONE, NONE, -1, True, False)]
+
+
+def _with(rows, q, **fields):
+    names = ("src", "e0", "e1", "e2", "out", "faces", "second_body")
+    row = list(rows[q])
+    for key, value in fields.items():
+        row[names.index(key)] = value
+    return [tuple(row) if i == q else r for i, r in enumerate(rows)]
+
+
+def test_descriptor_tables_the_package_does_not_produce(probe):
+    shape = (33, 70)
+    ask = lambda rows, ncomp, steps=5, shape=shape, **kw: header_mode(probe, rows, ncomp, shape, steps, **kw)      # noqa: E731
+    assert (ask(ONE, 1), ask(TWO, 2), ask(CHAIN, 1)) == (2, 3, 4)
+    assert ask(TWO, 2, steps=2) == 3 and ask(_with(TWO, 0, e0=NONE), 2) == 3 and ask(_with(CHAIN, 1, e0=NONE), 1) == 4
+    # a handle with a second body, in either pass
+    assert ask(_with(ONE, 0, second_body=True), 1) is None
+    for table, ncomp in ((TWO, 2), (CHAIN, 1)):
+        for q in (0, 1):
+            assert ask(_with(table, q, second_body=True), ncomp) is None
+    # extras[1] / extras[2] set, a pass without conditions, one field reading itself as e0
+    for table, ncomp in ((ONE, 1), (TWO, 2), (CHAIN, 1)):
+        for q in range(len(table)):
+            assert ask(_with(table, q, e1=0), ncomp) is None and ask(_with(table, q, e2=-1), ncomp) is None
+            assert ask(_with(table, q, faces=False), ncomp) is None
+    assert ask(_with(ONE, 0, e0=-1), 1) is None and ask(_with(ONE, 0, e0=0), 1) is None
+    assert ask(_with(TWO, 0, e0=-1), 2) is None and ask(_with(TWO, 1, e0=0), 2) is None and ask(_with(CHAIN, 0, e0=-1), 1) is None
+    # `out` pointing at a fixed array in a one-pass table; the chain broken; the wrong component counts; a third pass
+    assert ask(_with(ONE, 0, out=0), 1) is None and ask(_with(ONE, 0, src=0), 1) is None
+    assert ask(_with(CHAIN, 1, src=1), 1) is None and ask(_with(CHAIN, 0, out=-1), 1) is None and ask(_with(CHAIN, 1, out=0), 1) is None
+    assert ask(ONE, 2) is None and ask(TWO, 1) is None and ask(TWO, 3) is None and ask(CHAIN, 2) is None
+    assert ask(_with(TWO, 1, src=-1, out=-1), 2) is None
+    assert ask(TWO, 2, npasses=3) is None and ask(CHAIN, 1, npasses=3) is None
+    # steps, cells, dimensions, a boundary program
+    for table, ncomp in ((ONE, 1), (TWO, 2), (CHAIN, 1)):
+        assert ask(table, ncomp, steps=1) is None and ask(table, ncomp, steps=0) is None and ask(table, ncomp, steps=2) is not None
+        assert ask(table, ncomp, shape=(2, 1 << 20)) is not None and ask(table, ncomp, shape=(2, (1 << 20) + 1)) is None
+        assert ask(table, ncomp, shape=(1 << 21, 1)) is not None and ask(table, ncomp, shape=(2097153,)) is None
+        assert ask(table, ncomp, shape=(2, 33, 70)) is None and ask(table, ncomp, shape=(70,)) is None
+        assert ask(table, ncomp, bc_program=True) is None
+        # each knob: off; a limit of its own, at it and one above; the graph knob does not bear on the tile kernel
+        assert ask(table, ncomp, knobs=(0, 1 << 21, 0)) is None and ask(table, ncomp, knobs=(1, 1 << 21, 1)) is not None
+        assert ask(table, ncomp, knobs=(1, 33 * 70, 0)) is not None and ask(table, ncomp, knobs=(1, 33 * 70 - 1, 0)) is None
+
+
+def test_when_the_captured_block_is_replayed(probe):
+    """from the third step on, in whole blocks of 16, from four blocks on: 2 + 64 steps"""
+    ask = lambda uses_time, steps, comm=False, knobs=(1, 1 << 21, 1): bool(probe.jitplan_replay_applies(uses_time, steps, comm, _knobs(knobs)))   # noqa: E731
+    assert [ask(False, n) for n in (65, 66, 67)] == [False, True, True]
+    assert [ask(True, n) for n in (65, 66, 67)] == [False, False, False]
+    assert [ask(False, n, comm=True) for n in (65, 66, 67)] == [False, False, False]
+    assert [ask(False, n, knobs=(1, 1 << 21, 0)) for n in (65, 66, 67)] == [False, False, False]
+    assert [ask(False, n, knobs=None) for n in (65, 66, 67, 10 ** 6)] == [False] * 4          # the default: off
+    assert ask(False, 66, knobs=(0, 0, 1)) and ask(False, 10 ** 9) and not ask(False, 0) and not ask(False, 1)
+
+
+def test_the_loop_knobs_are_read_in_one_place(probe):
+    assert probe is not None      # (built: the children below load it)
+    worker = f"""
+import ctypes as C
+lib = C.CDLL({str(PROBE.parent / "_build" / "libjitplan_probe.so")!r})
+k = (C.c_long * 3)()
+lib.jitplan_loop_knobs_from_env(k)
+print(list(k))
+"""
+    def read(**env):
+        clean = {k: v for k, v in os.environ.items() if k not in ("PDEHIP_TILE2D", "PDEHIP_TILE2D_CELLS", "PDEHIP_JIT_GRAPH")}
+        out = subprocess.run([sys.executable, "-c", worker], env={**clean, **env}, capture_output=True, text=True, check=True).stdout
+        return eval(out)      # noqa: S307 - a list of three integers printed above
+
+    assert read() == [1, 1 << 21, 0]
+    assert read(PDEHIP_TILE2D="0") == [0, 1 << 21, 0] and read(PDEHIP_TILE2D="off") == [0, 1 << 21, 0] and read(PDEHIP_TILE2D="1") == [1, 1 << 21, 0]
+    assert read(PDEHIP_TILE2D_CELLS="4096", PDEHIP_JIT_GRAPH="1") == [1, 4096, 1] and read(PDEHIP_JIT_GRAPH="0") == [1, 1 << 21, 0]
+    jit, header = (HEADER.parent / "pdehip_jit.hip").read_text(), HEADER.read_text()
+    for knob in ("PDEHIP_TILE2D", "PDEHIP_TILE2D_CELLS", "PDEHIP_JIT_GRAPH"):
+        assert f'getenv("{knob}")' not in jit and header.count(f'getenv("{knob}")') == 1
+    assert jit.count("jitplan::loop_knobs_from_env()") == 1 and "static const jitplan::LoopKnobs k = jitplan::loop_knobs_from_env();" in jit

@@ -404,20 +404,37 @@ def face_class(faces_ptr, axis: int, n: int):
 def tile_route(eq, state, steps: int):
     """The mode in which the Euler loop of ``eq`` takes the tile kernel for ``steps`` steps, or None - decided as pdehip_jit_euler_run and
     plan_tile2d decide it, from the pass descriptors the package hands to the library.  Call inside ``shimlib.use_shim``."""
+    desc = loop_descriptors(eq, state)
+    if desc is None or desc[2]:
+        return None
+    passes, ncomp, _ = desc
+    shape = state.grid.shape
+    mode = loop_route(passes, ncomp, shape, steps)
+    if mode is None:
+        return None
+    classes = [[face_class(p.faces, a, shape[a]) for a in range(2)] for p in passes]
+    if any(c is None or c < 0 for cl in classes for c in cl) or any(cl != classes[0] for cl in classes):
+        return None
+    return mode
+
+
+def loop_descriptors(eq, state):
+    """(passes, components, "has a boundary program") as the package hands them to pdehip_jit_euler_run, or None where it does not call it.
+    Call inside ``shimlib.use_shim``."""
     backend = pde_hip.get_backend("hip")
     erhs = backend.make_expression_rhs(eq, state)
     if not erhs.has_loops:
         return None
     parts = getattr(erhs, "parts", None) or [erhs]
-    if not all(p.loop_ok() for p in parts) or any(p.bc_program() is not None for p in [erhs]):
+    if not all(p.loop_ok() for p in parts):
         return None
-    passes = list(erhs.loop_desc("euler")[0])
-    shape = state.grid.shape
-    mode = classify_passes(passes, len(parts) if getattr(erhs, "parts", None) else 1)
-    if mode is None or len(shape) != 2 or shape[0] * shape[1] > TILE_CELLS_DEFAULT or steps < 2:
-        return None
-    classes = [[face_class(p.faces, a, shape[a]) for a in range(2)] for p in passes]
-    if any(c is None or c < 0 for cl in classes for c in cl) or any(cl != classes[0] for cl in classes):
+    return list(erhs.loop_desc("euler")[0]), len(parts) if getattr(erhs, "parts", None) else 1, erhs.bc_program() is not None
+
+
+def loop_route(passes, ncomp: int, shape, steps: int, cells: int = TILE_CELLS_DEFAULT):
+    """The part of `tile_route` that ``jitplan::tile_mode`` (csrc/pdehip_jit_plan.h) decides: everything but the classes of the faces."""
+    mode = classify_passes(passes, ncomp)
+    if mode is None or len(shape) != 2 or shape[0] * shape[1] > cells or steps < 2:
         return None
     return mode
 
